@@ -1,8 +1,17 @@
 #!/usr/bin/env python
 """bench.py - interpolated frames/sec of the StableDiffusionWalkPipeline hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-size B]      (N > 1: bench.py spawns the N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-size B] [--dump-outputs DIR] [--full]
+                                                                              (N > 1: bench.py spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W untimed warm-up steps and K timed steps, and prints one JSON line with the headline `value`,
+`ms_per_step` (wall milliseconds of one timed step) and the roofline position of that number.  Everything else the line can
+carry - the per-kernel pass, the walk() passes, the parity self-check, the PNG rate, the CPU baseline and the other BASELINE
+configs (see "Extra objects" below) - runs only with ``--full``; the ``--no-*`` options switch single parts of it off.
+``--dump-outputs DIR`` writes the frames of the last timed step (uint8 values as float32, a seeded sample of frames when the
+batch exceeds 64 MB) to DIR/frames.npy and their frame indices to DIR/frame_index.npy, so that two builds can be compared
+output for output: with the same arguments the inputs are the same in every run.
 
 Multi-GPU: one process per GPU over RCCL.  Under torch.distributed.run the ranks come from the environment; a bare
 ``python bench.py --gpus N`` (no WORLD_SIZE) fans out by itself - it spawns N copies of this script with RANK / LOCAL_RANK /
@@ -20,9 +29,9 @@ encoding is outside `value` (reported separately as `png_frames_per_sec_per_core
 (no checkpoints offline) - the arithmetic is shape-identical.  With N > 1 every rank runs the same number of
 steps on its own frames (weak scaling, no data-path collective; the weights arrive by ONE RCCL broadcast).
 
-Extra objects in the JSON line:
+Extra objects in the JSON line (all but the first only with --full):
   roofline     whole hot path against the dense bf16 MFMA peak: achieved = 82.84 TFLOP/frame (SURVEY.md 8d,
-               algorithmic, padding not counted) x frames/s/GPU; plus `kernels`: per-kernel algorithmic
+               algorithmic, padding not counted) x frames/s/GPU; plus, with --full, `kernels`: per-kernel algorithmic
                TFLOP/s and share of GPU time from a HIP-event-bracketed eager pass (one UNet forward + one VAE
                decode of the same batch) run outside the timed region.
   attention    the UNet's 64x64-level self-attention: algorithmic / issued TFLOP/s (live) + PMC MFMA-busy share (committed profile)
@@ -58,7 +67,7 @@ MFMA_PEAK_TFLOPS = 2500.0                                 # MI355X dense bf16 (M
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (--config 3 times its fixed plan of batches instead)")
     ap.add_argument("--warmup", type=int, default=1)
     # frames per pipeline call = the reference's own `batch_size` argument.  128 measured 10.94 -> 11.28 frames/s over 64 (the
     # 8x8 / 16x16 UNet levels fill the 256 CUs better); 288 GB of HBM holds far more
@@ -71,12 +80,19 @@ def parse():
                          "contract); 3 = the literal 8-GPU config: 4 prompts, 240 frames in total, STRONG-scaled over the ranks")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"],
                     help="fp8 = BASELINE config 5: e4m3 operands in the UNet's ResBlock convs (everything else bf16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-walk-pass", action="store_true", help="skip the 60-frame walk() pass (frames/s including PNG files)")
-    ap.add_argument("--no-kernel-pass", action="store_true")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the self-check of the last batch (frames recomputed at batch 4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames of the last timed step to DIR/frames.npy (float32; a seeded sample of frames beyond 64 MB) "
+                         "and their indices in the batch to DIR/frame_index.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline number: per-kernel pass, walk() passes, parity self-check, PNG rate, "
+                         "CPU baseline, other BASELINE configs (each can be switched off with its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
+    ap.add_argument("--no-walk-pass", action="store_true", help="(--full) skip the 60-frame walk() pass (frames/s including PNG files)")
+    ap.add_argument("--no-kernel-pass", action="store_true", help="(--full) skip the per-kernel HIP-event pass")
+    ap.add_argument("--no-parity-check", action="store_true",
+                    help="(--full) skip the self-check of the last batch (frames recomputed at batch 4)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short passes of BASELINE configs 4 (SD-2.1 768x768) and 5 (fp8) that ride in `other_configs`")
+                    help="(--full) skip the short passes of BASELINE configs 4 (SD-2.1 768x768) and 5 (fp8) that ride in `other_configs`")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="spawn the ranks, form the process group (gloo without GPUs), all-reduce once, print the line - no model")
     return ap.parse_args()
@@ -523,6 +539,23 @@ def cpu_baseline(pipe_cfgs, size, inference_steps):
                       f"({per_frame:.1f} s/frame)"}
 
 
+DUMP_BYTES = 60 << 20          # frames written by --dump-outputs, over all ranks (the limit is 64 MB in all)
+
+
+def dump_outputs(out_dir, frames_u8, rank, world):
+    """--dump-outputs: the uint8 NHWC frames the last timed step returned, as float32 (exact).  A batch larger than this rank's
+    share of DUMP_BYTES is represented by a fixed sample of whole frames (seeded, sorted); frame_index.npy names them."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n = frames_u8.shape[0]
+    per_frame = 4 * int(np.prod(frames_u8.shape[1:]))
+    k = max(1, min(n, DUMP_BYTES // world // per_frame))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(20240).choice(n, size=k, replace=False))
+    sfx = "" if world == 1 else f"_rank{rank}"
+    np.save(out / f"frames{sfx}.npy", frames_u8[idx].astype(np.float32))
+    np.save(out / f"frame_index{sfx}.npy", idx.astype(np.float64))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -632,6 +665,8 @@ def main():
         "config": {"workload": workload, "batch_size": B, "frames": frames, "parallelism": f"frame-sharded dp{world}",
                    "hipgraph": pipe.use_graphs, "baseline_config": args.config},
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
     if rank == 0:
         if flop_per_frame and args.inference_steps == 50:
             ach = fps / world * flop_per_frame / 1e12
@@ -641,7 +676,7 @@ def main():
         else:
             result["roofline"] = {"bound": "mfma", "achieved": None, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                                   "frac": None, "traffic": None}
-        if not args.no_kernel_pass:
+        if args.full and not args.no_kernel_pass:
             _, embeds, noise = next(pipe.generate_inputs("a cat", "a dog", 42, 1337, (1, 4, h, h), my_T[:B], B))
             kp = kernel_pass(pipe, embeds, noise, size, args.inference_steps)
             shapes = kp.pop("_unet_shapes")
@@ -668,7 +703,7 @@ def main():
             att = attention_object(shapes, pmc)
             if att:
                 result["attention"] = att
-        if world == 1 and args.config == 2 and not args.no_walk_pass:
+        if args.full and world == 1 and args.config == 2 and not args.no_walk_pass:
             # the LITERAL BASELINE config 2 through the public API: walk() of 2 prompts, 60 interpolated frames, files and all
             # (lerp / slerp, 50-step loop, VAE, D2H, PNG encode + write by the asynchronous writer pool); make_video=False
             import shutil
@@ -699,23 +734,24 @@ def main():
                 result["walk_60_frames"]["cold_start_s"] = round(dt - dt2, 3)
             finally:
                 shutil.rmtree(tmp, ignore_errors=True)
-        if args.config == 2 and not args.no_parity_check:
+        if args.full and args.config == 2 and not args.no_parity_check:
             result["parity_check"] = parity_check(pipe, last_in[0][0], last_in[0][1], last, size, args.inference_steps)
-        # host-side PNG encode rate (outside `value`; the reference pays it serially at :553)
-        from PIL import Image
-        import io
-        img = Image.fromarray(last[0])
-        t1 = time.perf_counter()
-        for _ in range(3):
-            img.save(io.BytesIO(), format="PNG")
-        result["png_frames_per_sec_per_core"] = round(3 / (time.perf_counter() - t1), 2)
-        if world == 1 and not args.no_cpu_baseline and args.arch != "tiny":
+        if args.full:
+            # host-side PNG encode rate (outside `value`; the reference pays it serially at :553)
+            from PIL import Image
+            import io
+            img = Image.fromarray(last[0])
+            t1 = time.perf_counter()
+            for _ in range(3):
+                img.save(io.BytesIO(), format="PNG")
+            result["png_frames_per_sec_per_core"] = round(3 / (time.perf_counter() - t1), 2)
+        if args.full and world == 1 and not args.no_cpu_baseline and args.arch != "tiny":
             try:
                 result["cpu_baseline"] = cpu_baseline(cfgs_for_cpu, size, args.inference_steps)
             except Exception as exc:  # the GPU number must still be reported
                 result["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": os.cpu_count(), "kind": "port",
                                           "sample": f"failed: {exc!r}"}
-        if (world == 1 and args.config == 2 and args.arch == "sd14" and args.dtype == "bf16" and size == 512 and
+        if (args.full and world == 1 and args.config == 2 and args.arch == "sd14" and args.dtype == "bf16" and size == 512 and
                 args.inference_steps == 50 and not args.no_other_configs):
             # BASELINE configs 4 and 5 on this GPU, short passes with their own warm-up (the headline `value` above stays
             # config 2 in bf16).  The bf16 pipeline's graphs and buffers go first.

@@ -50,3 +50,30 @@ def test_a_torchrun_environment_is_used_as_is_and_checked():
 def test_a_failing_rank_fails_the_launcher():
     r = _run("--gpus", "2", "--launcher-selftest", env=dict(SDV_BENCH_SELFTEST_FAIL_RANK="1"))
     assert r.returncode != 0 and "a rank exited with code" in r.stderr
+
+
+def test_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
+    """``--dump-outputs``: a batch that fits is written whole, a larger one as the same seeded sample of whole frames in every
+    run, float32, under 64 MB in all - also split over ranks."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_module", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = np.arange(4 * 8 * 8 * 3, dtype=np.uint8).reshape(4, 8, 8, 3)
+    bench.dump_outputs(tmp_path / "s", small, 0, 1)
+    f = np.load(tmp_path / "s" / "frames.npy")
+    assert f.dtype == np.float32 and np.array_equal(f, small) and np.array_equal(np.load(tmp_path / "s" / "frame_index.npy"), np.arange(4))
+    big = np.random.default_rng(0).integers(0, 256, size=(128, 512, 512, 3), dtype=np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, big, 0, 1)
+    idx = np.load(tmp_path / "a" / "frame_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_index.npy")) and np.all(np.diff(idx) > 0) and 1 < len(idx) < 128
+    fa = np.load(tmp_path / "a" / "frames.npy")
+    assert np.array_equal(fa, big[idx.astype(int)].astype(np.float32))
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    for r in range(2):
+        bench.dump_outputs(tmp_path / "two", big, r, 2)
+    assert sum(p.stat().st_size for p in (tmp_path / "two").iterdir()) <= 64 << 20
+    assert sorted(p.name for p in (tmp_path / "two").iterdir()) == ["frame_index_rank0.npy", "frame_index_rank1.npy",
+                                                                     "frames_rank0.npy", "frames_rank1.npy"]

@@ -674,7 +674,7 @@ def test_bench_launches_its_own_ranks(hip, dev):
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--arch", "tiny", "--steps", "1", "--warmup", "1",
-                        "--batch-size", "4", "--no-cpu-baseline", "--no-walk-pass", "--no-kernel-pass"],
+                        "--batch-size", "4", "--full", "--no-cpu-baseline", "--no-walk-pass", "--no-kernel-pass"],
                        capture_output=True, text=True, env=dict(env, SDV_FORCE_DEVICE="0"), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -684,6 +684,29 @@ def test_bench_launches_its_own_ranks(hip, dev):
     if torch.cuda.device_count() < 8:
         r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "8"], capture_output=True, text=True, env=env, timeout=120)
         assert r.returncode != 0 and not r.stdout.strip() and "refusing" in r.stderr
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_last_frames(hip, dev, tmp_path):
+    """A plain ``bench.py`` run (no --full) times exactly --steps steps, carries none of the --full extras, and
+    ``--dump-outputs`` writes the last timed step's frames (float32 copies of the uint8 values)."""
+    import os
+    import subprocess
+    import sys
+    root = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--arch", "tiny", "--steps", "3", "--warmup", "1",
+                        "--batch-size", "4", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["config"]["frames"] == 12 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and "metric" in d
+    assert not {"parity_check", "cpu_baseline", "walk_60_frames", "other_configs", "png_frames_per_sec_per_core"} & set(d)
+    frames = np.load(tmp_path / "out" / "frames.npy")
+    assert frames.dtype == np.float32 and frames.shape == (4, 128, 128, 3)
+    assert np.array_equal(frames, np.round(frames)) and frames.min() >= 0 and frames.max() <= 255 and frames.std() > 0
+    assert np.array_equal(np.load(tmp_path / "out" / "frame_index.npy"), np.arange(4))
 
 
 def test_ragged_last_batch_reuses_the_captured_graph(hip, dev, tmp_path):
