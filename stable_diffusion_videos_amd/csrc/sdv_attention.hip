@@ -857,6 +857,9 @@ extern "C" int sdv_attention_bf16(const sdv_bf16* Q, const sdv_bf16* K, const sd
         }
     }
     SDV_REQUIRE(ldv >= ((Lk + 63) / 64) * 64, "sdv_attention_bf16: ldv=%d must cover roundup(Lk=%d, 64)", ldv, Lk);
+    // (the kernels address a (sample, head)'s K rows and V^T rows through 31-bit buffer ranges, whichever form V takes)
+    SDV_REQUIRE(((long long)(Lk - 1) * ldk + dh) * 2 < 0x7fffffffLL && (long long)dh * ldv * 2 < 0x7fffffffLL,
+                "sdv_attention_bf16: one sample's K rows / one head's V^T rows must span less than 2 GiB");
     switch (dh) {
         case 40: return launch_attention<40, false>(Q, K, Vt, O, B, H, Lq, Lk, ldq, ldk, ldv, ldo, scale, causal, s);
         case 64: return launch_attention<64, false>(Q, K, Vt, O, B, H, Lq, Lk, ldq, ldk, ldv, ldo, scale, causal, s);

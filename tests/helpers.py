@@ -52,3 +52,29 @@ def vae_pair(c: cfgs.VAEConfig, device, seed=1, tiled=False):
     from stable_diffusion_videos_amd.engine import VAEDecoderEngine
     sd = weights.synthetic_state_dict(weights.vae_decoder_shapes(c), seed=seed)
     return make_oracle_vae(c, sd), VAEDecoderEngine(c, sd, device, tiled=tiled)
+
+
+def _half_ulp_ratio(out64, ref64, mag64, acc_eps=1e-5):
+    """|out - ref| relative to (half a bf16 ulp of the result + fp32 accumulation noise acc_eps * sum |terms|)."""
+    ulp = torch.exp2(torch.floor(torch.log2(torch.maximum(ref64.abs(), out64.abs()).clamp_min(1e-30))) - 7)
+    return (out64 - ref64).abs() / (0.5 * ulp * (1 + 1e-3) + acc_eps * mag64)
+
+
+def _attn_ref64(q, k, v, heads, scale, causal=False):
+    """float64 softmax(QK^T scale) V per head, plus sum_k p_k |v_k| (the scale of the P-rounding error).
+    ``causal``: query i sees the keys j <= i."""
+    B, Lq, Cc = q.shape
+    dh = Cc // heads
+    out = torch.empty((B, Lq, Cc), dtype=torch.float64)
+    mag = torch.empty_like(out)
+    hidden = torch.ones((Lq, k.shape[1]), dtype=torch.bool).triu(1) if causal else None
+    for b in range(B):
+        for h in range(heads):
+            sl = slice(h * dh, (h + 1) * dh)
+            s = q[b, :, sl] @ k[b, :, sl].T * scale
+            if causal:
+                s = s.masked_fill(hidden, float("-inf"))
+            p = torch.softmax(s, -1)
+            out[b, :, sl] = p @ v[b, :, sl]
+            mag[b, :, sl] = p @ v[b, :, sl].abs()
+    return out, mag

@@ -55,6 +55,11 @@ def test_argument_validation_without_gpu(hip):
     # row-major V (ABI 10): ldv is a ROW stride and must cover the H * dh columns of a token
     assert lib.sdv_attention_bf16(16, 16, 16, 16, 1, 8, 64, 64, 40, 960, 960, 64, 320, 1.0, 0, 1, 1, None) == -1
     assert b"row-major V" in lib.sdv_last_error()
+    # a sample's K rows are addressed through a 31-bit buffer range in BOTH V forms: (2^20 + 1) keys x 1024 columns x 2 bytes = 2 GiB
+    big = (1 << 20) + 1
+    for vrm, ldv in ((0, big + 63), (1, 1024)):
+        assert lib.sdv_attention_bf16(16, 16, 16, 16, 1, 8, 64, big, 64, 1024, 1024, ldv, 512, 1.0, 0, 1, vrm, None) == -1
+        assert b"less than 2 GiB" in lib.sdv_last_error(), (vrm, lib.sdv_last_error())
     a.K = 64
     a.tile = 14                                                 # the transposed tile of ABI 9
     assert lib.sdv_gemm_bf16(ctypes.byref(a), None) == -1 and b"bad tile" in lib.sdv_last_error()

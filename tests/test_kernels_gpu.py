@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, bf16_round, rel_l2
+from helpers import _attn_ref64, _half_ulp_ratio
 
 pytestmark = pytest.mark.gpu
 
@@ -306,12 +307,6 @@ def test_conv3x3(hip, dev, tile, mode, circular, n, H, W, Cin, Cout):
     assert rel_l2(out.float().reshape(ref.shape), ref) < MFMA_TOL
 
 
-def _half_ulp_ratio(out64, ref64, mag64, acc_eps=1e-5):
-    """|out - ref| relative to (half a bf16 ulp of the result + fp32 accumulation noise acc_eps * sum |terms|)."""
-    ulp = torch.exp2(torch.floor(torch.log2(torch.maximum(ref64.abs(), out64.abs()).clamp_min(1e-30))) - 7)
-    return (out64 - ref64).abs() / (0.5 * ulp * (1 + 1e-3) + acc_eps * mag64)
-
-
 @pytest.mark.parametrize("tile,mode", [(0, 1), (6, 1), (1, 1), (0, 2), (0, 3)])
 def test_conv3x3_is_correctly_rounded(hip, dev, tile, mode):
     """Parity ladder step 2 for the implicit-GEMM conv on the UNet's real 64x64-level shape (320 -> 320 channels, 64 x 64
@@ -585,21 +580,6 @@ def test_attention(hip, dev, dh, Lq, Lk):
     assert rel_l2(out_r.float().view(B, Lq, Cc), ref) < 6e-3
     if Lk > 128 or dh == 160:
         assert torch.equal(out_r, out), "row-major V and transposed V must give the same bits"
-
-
-def _attn_ref64(q, k, v, heads, scale):
-    """float64 softmax(QK^T scale) V per head, plus sum_k p_k |v_k| (the scale of the P-rounding error)."""
-    B, Lq, Cc = q.shape
-    dh = Cc // heads
-    out = torch.empty((B, Lq, Cc), dtype=torch.float64)
-    mag = torch.empty_like(out)
-    for b in range(B):
-        for h in range(heads):
-            sl = slice(h * dh, (h + 1) * dh)
-            p = torch.softmax(q[b, :, sl] @ k[b, :, sl].T * scale, -1)
-            out[b, :, sl] = p @ v[b, :, sl]
-            mag[b, :, sl] = p @ v[b, :, sl].abs()
-    return out, mag
 
 
 @pytest.mark.parametrize("vrm", [False, True])
