@@ -359,6 +359,38 @@ int sdv_rgb_u8_to_bf16_c4(const uint8_t* in, sdv_bf16* out, int64_t npix, float 
 int sdv_axpby_bf16(const sdv_bf16* a, int32_t lda, const sdv_bf16* b, int32_t ldb, sdv_bf16* out, int32_t ldo,
                    int64_t rows, int32_t cols, float alpha, float beta, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Safety checker (stable_diffusion_pipeline.py:440-447).  The CLIP vision tower between these two entry points runs on
+ * sdv_gemm_bf16 / sdv_layernorm_bf16 / sdv_attention_bf16 (vision.py); csrc/sdv_vision.hip holds what is not a transformer.
+ *
+ * sdv_clip_preprocess_patches - replaces `self.feature_extractor(self.numpy_to_pil(image), return_tensors="pt")` (:441,
+ * transformers.CLIPImageProcessor) AND the im2col of the stride-P patch convolution, in one launch:
+ *   frames   uint8 RGB NHWC [n][H][W][3], contiguous (what the VAE image epilogue leaves in HBM)
+ *   patches  bf16 [n * (S/P)^2][Kpad], 16-byte aligned: row = patch (image-major, then raster), column = (c, py, px), i.e. the
+ *            flattened conv weight [hidden][3][P][P] is the GEMM's W; K = 3*P*P zero-padded to Kpad = roundup(K, 64) - the pad
+ *            columns are written (as zeros) by the kernel
+ *   x_* / y_* the two 1-D tap tables of PIL's bicubic resize (separable, a = -0.5, support 2*max(scale, 1), centre (i + 0.5)*scale,
+ *            weights normalised to sum 1) restricted to the centre-crop window: for each of the S output samples of an axis the
+ *            first source index (`off` int32 [S]), the tap count (`cnt` int32 [S], <= taps) and the weights (`w` fp32 [S][taps])
+ *   host_mean / host_std   HOST pointers to 3 floats: value = (pixel / 255 - mean[c]) / std[c]
+ * Both passes are fp32 with the horizontally filtered rows staged in LDS (no uint8 rounding between them, no resized image in
+ * HBM); only the crop window is computed.  P * S * 12 + S * 12 bytes must fit in 64 KiB of LDS.
+ *
+ * sdv_safety_screen - replaces `self.safety_checker(images=image, clip_input=...)` behind the vision tower (:442-447, diffusers
+ * StableDiffusionSafetyChecker.forward) and `images[idx] = np.zeros(...)`:
+ *   cos = cosine similarity of image_embeds [n][D] with special_care_embeds [n_special][D] / concept_embeds [n_concept][D] (fp32);
+ *   special = cos_s - special_thr (+ 0);  adj = 0.01 if any special > 0 else 0;  concept = cos_c - concept_thr + adj;
+ *   flags[i] = any(concept > 0);  scores [n][n_special + n_concept] = [special | concept].
+ *   frames (may be NULL; else 16-byte aligned, n frames of frame_bytes bytes each): flagged frames are overwritten with zeros.
+ * Two launches on `stream` (head, black-out). */
+int sdv_clip_preprocess_patches(const uint8_t* frames, sdv_bf16* patches, int32_t n, int32_t H, int32_t W, int32_t S, int32_t P,
+                                int32_t Kpad, const int32_t* x_off, const int32_t* x_cnt, const float* x_w, int32_t x_taps,
+                                const int32_t* y_off, const int32_t* y_cnt, const float* y_w, int32_t y_taps,
+                                const float* host_mean, const float* host_std, void* stream);
+int sdv_safety_screen(const float* image_embeds, const float* concept_embeds, const float* special_care_embeds,
+                      const float* concept_thr, const float* special_thr, int32_t n, int32_t D, int32_t n_concept,
+                      int32_t n_special, uint8_t* frames, int64_t frame_bytes, int32_t* flags, float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,9 +9,10 @@ from .image_generation import generate_images
 from .pipeline import StableDiffusionPipelineOutput, StableDiffusionWalkPipeline
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
                         LMSDiscreteScheduler, PNDMScheduler)
+from .vision import SafetyCheckerEngine
 from .utils import get_timesteps_arr, make_video_pyav, pad_along_axis, slerp
 
 __version__ = "0.1.0"
 __all__ = ["StableDiffusionWalkPipeline", "StableDiffusionPipelineOutput", "DDIMScheduler", "PNDMScheduler",
            "LMSDiscreteScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler", "DPMSolverMultistepScheduler",
-           "slerp", "get_timesteps_arr", "make_video_pyav", "pad_along_axis", "generate_images"]
+           "slerp", "get_timesteps_arr", "make_video_pyav", "pad_along_axis", "generate_images", "SafetyCheckerEngine"]

@@ -35,7 +35,9 @@ EXTRA_FLAGS = {"sdv_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "sdv_gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
                # fused feed-forward: one wave per SIMD with all 512 registers (AGPR-form MFMAs: no vgpr-form here); its VALU stream is
                # laid out by hand beside the MFMAs, where packed fp32 ops (v_pk_fma_f32 out of the SLP vectoriser) are an anti-lever
-               "sdv_ffn.hip": ["-fno-slp-vectorize"]}
+               "sdv_ffn.hip": ["-fno-slp-vectorize"],
+               # safety-checker glue (resize + patches, cosine head): plain fp32 arithmetic, no packed ops either (IEEE division: not FAST_MATH)
+               "sdv_vision.hip": ["-fno-slp-vectorize"]}
 
 
 def hipcc() -> str:

@@ -69,6 +69,51 @@ class TextConfig:
     eos_token_id: int = 49407
 
 
+@dataclass
+class VisionConfig:
+    """CLIP vision tower + projection of the safety checker (``transformers.CLIPVisionModelWithProjection``; the defaults are
+    ViT-L/14 at 224 x 224, what ``StableDiffusionSafetyChecker`` of a stock SD checkpoint holds) and the checker head's sizes."""
+    hidden_size: int = 1024
+    intermediate_size: int = 4096
+    num_hidden_layers: int = 24
+    num_attention_heads: int = 16
+    image_size: int = 224
+    patch_size: int = 14
+    projection_dim: int = 768
+    hidden_act: str = "quick_gelu"
+    layer_norm_eps: float = 1e-5
+    num_concepts: int = 17
+    num_special_care: int = 3
+
+    @property
+    def num_tokens(self) -> int:
+        return (self.image_size // self.patch_size) ** 2 + 1
+
+
+def sd_vision() -> VisionConfig:
+    return VisionConfig()
+
+
+def tiny_vision() -> VisionConfig:
+    return VisionConfig(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2, image_size=56,
+                        projection_dim=64)       # head dim 64 as in ViT-L/14, 17 tokens
+
+
+def vision_from_json(path) -> VisionConfig:
+    """``safety_checker/config.json``: a CLIPConfig whose ``vision_config`` (``vision_config_dict`` in old files) describes the
+    tower; ``projection_dim`` sits at the top level."""
+    data = json.loads(Path(path).read_text())
+    vis = dict(data.get("vision_config_dict") or {})
+    vis.update(data.get("vision_config") or {})
+    if not vis and "hidden_size" in data:
+        vis = data                                  # a bare CLIPVisionConfig
+    names = {f.name for f in fields(VisionConfig)}
+    kw = {k: v for k, v in vis.items() if k in names and k != "projection_dim"}
+    if "projection_dim" in data:
+        kw["projection_dim"] = data["projection_dim"]
+    return VisionConfig(**kw)
+
+
 def sd14_unet() -> UNetConfig:
     return UNetConfig()
 

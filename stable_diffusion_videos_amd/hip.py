@@ -90,6 +90,9 @@ _SIGNATURES = {
     "sdv_rgb_u8_to_bf16_c4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "sdv_axpby_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                  C.c_float, C.c_float, C.c_void_p]),
+    "sdv_clip_preprocess_patches": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 +
+                                    [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
+    "sdv_safety_screen": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1052,3 +1055,107 @@ _k_f32_to_bf16 = _defop("k_f32_to_bf16(Tensor x) -> Tensor", _f32_to_bf16_impl, 
 
 def f32_to_bf16(x: torch.Tensor) -> torch.Tensor:
     return _k_f32_to_bf16(x)
+
+
+# ------------------------------------------------------------------------------------------------
+# safety checker glue (csrc/sdv_vision.hip): frames -> patch rows, cosine head + black-out
+# ------------------------------------------------------------------------------------------------
+def patch_kpad(P: int) -> int:
+    """K = 3 * P * P of the patch-embedding GEMM rounded up to sdv_gemm_bf16's K granularity (588 -> 640 for P = 14)."""
+    return (3 * P * P + 63) // 64 * 64
+
+
+def _clip_preprocess_impl(frames, patches, x_off, x_cnt, x_w, y_off, y_cnt, y_w, S, P, mean, std):
+    # every check comes before the first pointer is taken
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise SdvHipError(f"clip_preprocess: frames must be a contiguous uint8 [n, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)} "
+                          f"strides {frames.stride()}")
+    n, H, W, _ = frames.shape
+    if n < 1 or S < 1 or P < 1 or S % P:
+        raise SdvHipError(f"clip_preprocess: bad geometry n={n} S={S} P={P} (S % P == 0)")
+    G, Kpad = S // P, patch_kpad(P)
+    if patches.dtype != BF16 or patches.dim() != 2 or patches.shape[1] != Kpad or patches.stride(1) != 1 or patches.stride(0) != Kpad:
+        raise SdvHipError(f"clip_preprocess: patches must be dense bf16 rows of Kpad = {Kpad} columns, got {patches.dtype} {tuple(patches.shape)} "
+                          f"strides {patches.stride()}")
+    if patches.shape[0] != n * G * G:
+        raise SdvHipError(f"clip_preprocess: patches has {patches.shape[0]} rows, {n} frames x {G} x {G} patches need {n * G * G}")
+    if patches.data_ptr() % 16:
+        raise SdvHipError("clip_preprocess: patches must be 16-byte aligned")
+    for name, off, cnt, w, size in (("x", x_off, x_cnt, x_w, W), ("y", y_off, y_cnt, y_w, H)):
+        if off.dtype != torch.int32 or cnt.dtype != torch.int32 or w.dtype != F32 or not (off.is_contiguous() and cnt.is_contiguous() and w.is_contiguous()):
+            raise SdvHipError(f"clip_preprocess: {name} tap tables must be contiguous int32 / int32 / fp32")
+        if off.numel() != S or cnt.numel() != S or w.dim() != 2 or w.shape[0] != S or not 1 <= w.shape[1] <= size:
+            raise SdvHipError(f"clip_preprocess: {name} tap tables must hold S = {S} entries ([S], [S], [S, taps <= {size}]), got {off.numel()} / "
+                              f"{cnt.numel()} / {tuple(w.shape)}")
+    if len(mean) != 3 or len(std) != 3:
+        raise SdvHipError("clip_preprocess: image_mean / image_std hold one value per RGB channel")
+    lib = load()
+    args = (_ptr(frames, torch.uint8, "frames"), _ptr(patches, BF16, "patches"), n, H, W, S, P, Kpad,
+            _ptr(x_off, torch.int32, "x_off"), _ptr(x_cnt, torch.int32, "x_cnt"), _ptr(x_w, F32, "x_w"), x_w.shape[1],
+            _ptr(y_off, torch.int32, "y_off"), _ptr(y_cnt, torch.int32, "y_cnt"), _ptr(y_w, F32, "y_w"), y_w.shape[1],
+            (C.c_float * 3)(*mean), (C.c_float * 3)(*std))
+    _launch("clip_preprocess", dict(bytes=3.0 * n * H * W + 2.0 * patches.numel()),
+            lambda: _check(lib.sdv_clip_preprocess_patches(*args, _stream()), "sdv_clip_preprocess_patches"))
+
+
+_k_clip_preprocess = _defop("k_clip_preprocess(Tensor frames, Tensor(a!) patches, Tensor x_off, Tensor x_cnt, Tensor x_w, Tensor y_off, Tensor y_cnt, "
+                            "Tensor y_w, int S, int P, float[] mean, float[] std) -> ()", _clip_preprocess_impl)
+
+
+def clip_preprocess_patches(frames: torch.Tensor, taps_x, taps_y, *, S: int, P: int, mean, std, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 RGB NHWC frames [n, H, W, 3] -> bf16 patch rows [n * (S/P)^2, Kpad] of the CLIP patch-embedding GEMM
+    (``torch.ops.sdv.k_clip_preprocess`` -> sdv_clip_preprocess_patches): PIL-bicubic resize of the shortest edge to ``S``, centre
+    crop, / 255, (x - mean) / std, im2col in (c, py, px) order.  ``taps_x`` / ``taps_y``: (off int32 [S], cnt int32 [S], w fp32
+    [S, taps]) on the device, from ``vision.resample_taps``."""
+    if out is None:
+        out = torch.empty((frames.shape[0] * (S // P) ** 2, patch_kpad(P)), dtype=BF16, device=frames.device)
+    _k_clip_preprocess(frames, out, *taps_x, *taps_y, int(S), int(P), [float(v) for v in mean], [float(v) for v in std])
+    return out
+
+
+def _safety_screen_impl(image_embeds, concept, special, thr_c, thr_s, frames, flags, scores):
+    if image_embeds.dtype != F32 or image_embeds.dim() != 2 or not image_embeds.is_contiguous():
+        raise SdvHipError(f"safety_screen: image_embeds must be contiguous fp32 [n, D], got {image_embeds.dtype} {tuple(image_embeds.shape)}")
+    n, D = image_embeds.shape
+    for name, t in (("concept_embeds", concept), ("special_care_embeds", special)):
+        if t.dtype != F32 or t.dim() != 2 or t.shape[1] != D or not t.is_contiguous():
+            raise SdvHipError(f"safety_screen: {name} must be contiguous fp32 [rows, D = {D}], got {t.dtype} {tuple(t.shape)}")
+    nc, ns = concept.shape[0], special.shape[0]
+    if nc < 1 or nc + ns > 64:
+        raise SdvHipError(f"safety_screen: at most 64 concept + special-care rows, got {nc} + {ns}")
+    if thr_c.dtype != F32 or thr_s.dtype != F32 or thr_c.numel() != nc or thr_s.numel() != ns or not (thr_c.is_contiguous() and thr_s.is_contiguous()):
+        raise SdvHipError(f"safety_screen: thresholds must be contiguous fp32 vectors of {nc} / {ns} elements, got {thr_c.numel()} / {thr_s.numel()}")
+    if flags.dtype != torch.int32 or flags.numel() != n or not flags.is_contiguous():
+        raise SdvHipError(f"safety_screen: flags must be a contiguous int32 vector of n = {n} elements, got {flags.dtype} x {flags.numel()}")
+    if scores.dtype != F32 or tuple(scores.shape) != (n, ns + nc) or not scores.is_contiguous():
+        raise SdvHipError(f"safety_screen: scores must be contiguous fp32 [{n}, {ns + nc}], got {scores.dtype} {tuple(scores.shape)}")
+    frame_bytes = 0
+    if frames is not None:
+        if frames.dtype != torch.uint8 or frames.dim() < 2 or frames.shape[0] != n or not frames.is_contiguous() or frames.numel() == 0:
+            raise SdvHipError(f"safety_screen: frames must be a contiguous uint8 tensor of n = {n} frames, got {frames.dtype} {tuple(frames.shape)} "
+                              f"strides {frames.stride()}")
+        if frames.data_ptr() % 16:
+            raise SdvHipError("safety_screen: frames must be 16-byte aligned")
+        frame_bytes = frames.numel() // n
+    lib = load()
+    args = (_ptr(image_embeds, F32, "image_embeds"), _ptr(concept, F32, "concept_embeds"), _ptr(special, F32, "special_care_embeds"),
+            _ptr(thr_c, F32, "concept_thr"), _ptr(thr_s, F32, "special_thr"), n, D, nc, ns, _ptr(frames, torch.uint8, "frames"), frame_bytes,
+            _ptr(flags, torch.int32, "flags"), _ptr(scores, F32, "scores"))
+    _launch("safety_screen", dict(bytes=4.0 * D * (n + nc + ns)),
+            lambda: _check(lib.sdv_safety_screen(*args, _stream()), "sdv_safety_screen"))
+
+
+_k_safety_screen = _defop("k_safety_screen(Tensor image_embeds, Tensor concept, Tensor special, Tensor thr_c, Tensor thr_s, Tensor(a!)? frames, "
+                          "Tensor(b!) flags, Tensor(c!) scores) -> ()", _safety_screen_impl)
+
+
+def safety_screen(image_embeds: torch.Tensor, concept: torch.Tensor, special: torch.Tensor, thr_c: torch.Tensor, thr_s: torch.Tensor,
+                  frames: Optional[torch.Tensor] = None):
+    """The head of diffusers' ``StableDiffusionSafetyChecker`` and the black-out of the flagged frames
+    (``torch.ops.sdv.k_safety_screen`` -> sdv_safety_screen): returns (flags int32 [n], scores fp32 [n, special + concept]), both on
+    the device; flagged ``frames`` (uint8, n leading) are zeroed in place."""
+    n = image_embeds.shape[0]
+    flags = torch.empty((n,), dtype=torch.int32, device=image_embeds.device)
+    scores = torch.empty((n, special.shape[0] + concept.shape[0]), dtype=F32, device=image_embeds.device)
+    _k_safety_screen(image_embeds, concept, special, thr_c, thr_s, frames, flags, scores)
+    return flags, scores

@@ -43,6 +43,7 @@ from .engine import UNetEngine, VAEDecoderEngine
 from .scheduler import DDIMScheduler, adopt as adopt_scheduler
 from .text import build_text_encoder, load_tokenizer
 from .utils import FrameWriter, get_timesteps_arr, make_video_pyav, numpy_to_pil
+from .vision import SafetyCheckerEngine
 
 logger = logging.getLogger("stable_diffusion_videos_amd")
 
@@ -143,7 +144,10 @@ class StableDiffusionWalkPipeline:
         {"sd14", "sd21", "tiny"}; inferred from the name).  ``tiled=True`` makes every convolution circular
         (the reference monkey-patches nn.Conv2d; here it is a kernel flag).  ``fp8=True`` (or
         ``torch_dtype="fp8"``): the UNet's ResBlock convolutions run on the fp8 (e4m3) MFMA path with per-tensor scales
-        calibrated on the first forward; everything else stays bf16 (BASELINE.json configs[4])."""
+        calibrated on the first forward; everything else stays bf16 (BASELINE.json configs[4]).
+        ``safety_checker``: None (default) = no checker, as before; True / "default" = the native ``SafetyCheckerEngine`` (reference
+        :440-447) from ``<dir>/safety_checker`` or, without one, seeded synthetic weights; a ``SafetyCheckerEngine`` is adopted;
+        anything else (a diffusers module) is refused when the pipeline is called."""
         name = str(pretrained_model_name_or_path or "")
         model_dir = None
         if name and Path(name).is_dir():
@@ -212,6 +216,13 @@ class StableDiffusionWalkPipeline:
         tokenizer = load_tokenizer(model_dir, tcfg)
         if vae is not None and not isinstance(vae, (_PendingModule, VAEDecoderEngine)):
             vae = _ForeignVAE(vae)
+        if safety_checker is True or (isinstance(safety_checker, str) and safety_checker == "default"):
+            from .vision import build_safety_checker
+            has_dir = model_dir is not None and (model_dir / "safety_checker" / "config.json").exists()
+            safety_checker = build_safety_checker(model_dir, seed=synthetic_seed + 3,
+                                                  cfg=cfgs.tiny_vision() if (arch == "tiny" and not has_dir) else None)
+        if isinstance(safety_checker, SafetyCheckerEngine) and feature_extractor is None:
+            feature_extractor = safety_checker.feature_extractor
         pipe = cls(vae=vae or _PendingModule("vae", vcfg, v_sd), text_encoder=text_encoder, tokenizer=tokenizer,
                    unet=_PendingModule("unet", ucfg, u_sd), scheduler=scheduler, safety_checker=safety_checker,
                    feature_extractor=feature_extractor, requires_safety_checker=False, text_config=tcfg)
@@ -251,6 +262,8 @@ class StableDiffusionWalkPipeline:
                 self.vae = VAEDecoderEngine(v.config, v_sd, device, tiled=self.tiled)
                 v.state_dict = None
         self.text_encoder.to(device)
+        if isinstance(self.safety_checker, SafetyCheckerEngine):
+            self.safety_checker.to(device)
         self._device = device
         self._uncond_cache.clear()
         return self
@@ -538,6 +551,9 @@ class StableDiffusionWalkPipeline:
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: Optional[int] = 1,
                  text_embeddings: Optional[torch.Tensor] = None, **kwargs):
         """Same contract as the reference ``__call__`` (:191-455)."""
+        if self.safety_checker is not None and not isinstance(self.safety_checker, SafetyCheckerEngine):
+            # (a diffusers / torch module: only the native engine runs here - said before the denoise loop, not after it)
+            raise NotImplementedError("safety_checker is outside the hot path; pass safety_checker=None")
         if isinstance(self.unet, _PendingModule):
             raise hip.SdvHipError("call pipeline.to('cuda') first: the hot path only exists as HIP kernels")
         t_start = time.perf_counter()
@@ -656,6 +672,16 @@ class StableDiffusionWalkPipeline:
         # "numpy_u8": rounded uint8 NHWC array, no PIL objects; "u8_cuda": the same array left in HBM (upsampler input)
         want_float = output_type not in ("pil", "numpy_u8", "u8_cuda")
         u8, f32 = self.vae.decode(ent["latents"], want_float=want_float)                         # :432-435
+        flags_host = None
+        if self.safety_checker is not None:                                                       # :440-447
+            # on the uint8 frames in HBM, before they leave it: flagged frames go out already black, and the flags ride on the same
+            # stream in front of the frames' own copy - whose wait is the only one
+            u8 = u8[:B_real].contiguous()
+            flags_dev, _ = self.safety_checker.screen(u8)
+            if want_float:
+                f32 = f32[:B_real] * (flags_dev == 0).to(f32.dtype).view(-1, 1, 1, 1)
+            flags_host = torch.empty((B_real,), dtype=torch.int32, pin_memory=True)
+            flags_host.copy_(flags_dev, non_blocking=True)
         if output_type == "u8_cuda":
             image = u8[:B_real]
         elif want_float:
@@ -665,8 +691,10 @@ class StableDiffusionWalkPipeline:
         t_done = time.perf_counter()
         self.last_timings = {"prepare_s": t_prep - t_start, "denoise_decode_s": t_done - t_prep, "frames": B_real}
         has_nsfw = None
-        if self.safety_checker is not None:
-            raise NotImplementedError("safety_checker is outside the hot path; pass safety_checker=None")
+        if flags_host is not None:
+            if output_type == "u8_cuda":
+                torch.cuda.current_stream().synchronize()      # (no frame copy to ride on)
+            has_nsfw = [bool(v) for v in flags_host.tolist()]
         if output_type == "pil":
             image = numpy_to_pil(image)                                                           # :450
         if not return_dict:

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import torch
 
-from .config import RRDBNetConfig, TextConfig, UNetConfig, VAEConfig
+from .config import RRDBNetConfig, TextConfig, UNetConfig, VAEConfig, VisionConfig
 
 StateDict = Dict[str, torch.Tensor]
 
@@ -160,6 +160,75 @@ def load_clip_text(model_dir: Path, shapes) -> StateDict:
     if path is None:
         raise FileNotFoundError(f"no text encoder weights under {d}")
     raw = {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in _load_file(path).items()}
+    missing = [k for k in shapes if k not in raw]
+    if missing:
+        raise KeyError(f"{path}: missing keys, e.g. {missing[:4]}")
+    out: StateDict = OrderedDict()
+    for k, shape in shapes.items():
+        t = raw[k].float()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{k}: shape {tuple(t.shape)} != expected {shape}")
+        out[k] = t
+    return out
+
+
+SAFETY_HEAD_KEYS = ("concept_embeds", "special_care_embeds", "concept_embeds_weights", "special_care_embeds_weights")
+
+
+def vision_shapes(cfg: VisionConfig) -> "OrderedDict[str, tuple]":
+    """``transformers.CLIPVisionModelWithProjection`` state-dict schema without the ``vision_model.`` prefix (``pre_layrnorm`` is
+    the upstream spelling), followed by the four buffers of diffusers' ``StableDiffusionSafetyChecker`` head."""
+    sd: "OrderedDict[str, tuple]" = OrderedDict()
+    D, I, P = cfg.hidden_size, cfg.intermediate_size, cfg.patch_size
+    sd["embeddings.class_embedding"] = (D,)
+    sd["embeddings.patch_embedding.weight"] = (D, 3, P, P)
+    sd["embeddings.position_embedding.weight"] = (cfg.num_tokens, D)
+    _norm(sd, "pre_layrnorm", D)
+    for i in range(cfg.num_hidden_layers):
+        p = f"encoder.layers.{i}"
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            _lin(sd, f"{p}.self_attn.{n}", D, D)
+        _norm(sd, f"{p}.layer_norm1", D)
+        _lin(sd, f"{p}.mlp.fc1", D, I)
+        _lin(sd, f"{p}.mlp.fc2", I, D)
+        _norm(sd, f"{p}.layer_norm2", D)
+    _norm(sd, "post_layernorm", D)
+    _lin(sd, "visual_projection", D, cfg.projection_dim, bias=False)
+    sd["concept_embeds"] = (cfg.num_concepts, cfg.projection_dim)
+    sd["special_care_embeds"] = (cfg.num_special_care, cfg.projection_dim)
+    sd["concept_embeds_weights"] = (cfg.num_concepts,)
+    sd["special_care_embeds_weights"] = (cfg.num_special_care,)
+    return sd
+
+
+def synthetic_safety_checker(cfg: VisionConfig, seed: int = 0) -> StateDict:
+    """Seeded stand-in of the same shapes: the tower as ``synthetic_state_dict`` makes it, class / position embeddings of the
+    patch embeddings' scale, unit-variance concept embeddings and thresholds around the real checker's (0.18 ... 0.22)."""
+    shapes = vision_shapes(cfg)
+    sd = synthetic_state_dict(OrderedDict((k, v) for k, v in shapes.items() if k not in SAFETY_HEAD_KEYS), seed=seed)
+    g = torch.Generator(device="cpu").manual_seed(seed + 7919)
+    sd["embeddings.class_embedding"] = bf16_round(torch.randn(shapes["embeddings.class_embedding"], generator=g))
+    sd["embeddings.position_embedding.weight"] = bf16_round(0.5 * torch.randn(shapes["embeddings.position_embedding.weight"], generator=g))
+    for k in ("concept_embeds", "special_care_embeds"):
+        sd[k] = torch.randn(shapes[k], generator=g)
+    for k in ("concept_embeds_weights", "special_care_embeds_weights"):
+        sd[k] = 0.18 + 0.04 * torch.rand(shapes[k], generator=g)
+    return sd
+
+
+def load_safety_checker(model_dir: Path, shapes) -> StateDict:
+    """``<model_dir>/safety_checker/{model.safetensors | pytorch_model.bin}``: the tower's keys are accepted with any number of
+    leading ``vision_model.`` prefixes (StableDiffusionSafetyChecker nests CLIPVisionModel: two; CLIPVisionModelWithProjection:
+    one; this package's own schema: none)."""
+    d = Path(model_dir) / "safety_checker"
+    path = next((p for p in (d / "model.safetensors", d / "model.fp16.safetensors", d / "pytorch_model.bin") if p.exists()), None)
+    if path is None:
+        raise FileNotFoundError(f"no safety checker weights under {d}")
+    raw: StateDict = {}
+    for k, v in _load_file(path).items():
+        while k.startswith("vision_model."):
+            k = k[len("vision_model."):]
+        raw[k] = v
     missing = [k for k in shapes if k not in raw]
     if missing:
         raise KeyError(f"{path}: missing keys, e.g. {missing[:4]}")
