@@ -391,6 +391,32 @@ int sdv_safety_screen(const float* image_embeds, const float* concept_embeds, co
                       const float* concept_thr, const float* special_thr, int32_t n, int32_t D, int32_t n_concept,
                       int32_t n_special, uint8_t* frames, int64_t frame_bytes, int32_t* flags, float* scores, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG encoder (csrc/sdv_jpeg.hip).  Replaces the host-side JPEG compression of frames the GPU already holds: `image.save(frame_filepath)`
+ * in make_clip_frames for a `.jpg` image_file_ext (stable_diffusion_pipeline.py:553) and the frame encode inside make_video_pyav
+ * (utils.py:69-128) where the track is Motion-JPEG.  Only compressed bytes leave HBM.
+ *
+ * Stream: baseline sequential JFIF, 8 bit, 3 components, 4:2:0; MCU = 16 x 16 pixels = blocks Y00 Y01 Y10 Y11 Cb Cr; the frame is padded
+ * to multiples of 16 by replicating its last row / column; the Annex K "typical" Huffman tables; restart interval = one MCU row
+ * (ceil(W / 16) MCUs), RST0..RST7 cycling between the intervals, each interval padded to a byte with 1-bits, 0xFF stuffed with 0x00.
+ *
+ * sdv_jpeg_transform_u8   frames uint8 RGB NHWC [n][H][W][3] contiguous -> coef int16 [n][ceil(H/16)][ceil(W/16)][6][64] (16-byte
+ *   aligned), each block in zigzag order: JFIF full-range YCbCr, chroma = mean of each 2 x 2, - 128, orthonormal 8 x 8 DCT-II, divided
+ *   by the table entry, rounded to nearest with ties away from zero; fp32, nothing rounded in between.
+ *   qtab_luma / qtab_chroma: HOST pointers to 64 entries in natural (row-major) order, each 1 .. 255.
+ *
+ * sdv_jpeg_entropy_pack   coef -> out: n complete files back to back, out[offsets[k] .. offsets[k + 1]) is file k; offsets int64 [n + 1]
+ *   and needed int64 [1] (= offsets[n]) in GPU memory.  header: the header_len bytes SOI .. SOS that open every file (GPU memory,
+ *   constant for one (H, W, quality)).  scratch: at least 12 bytes per restart interval (n * ceil(H/16)), 8-byte aligned.
+ *   When *needed > out_cap NOTHING is written to out (offsets and needed still are): the caller retries with a buffer of *needed bytes.
+ *   Three launches on `stream`: count (one wave per restart interval), scan, write (the same code, storing at the final positions).
+ * 1 <= H, W <= 65535, 1 <= n <= 65535. */
+int sdv_jpeg_transform_u8(const uint8_t* frames, int32_t n, int32_t H, int32_t W, const uint16_t* qtab_luma,
+                          const uint16_t* qtab_chroma, int16_t* coef, void* stream);
+int sdv_jpeg_entropy_pack(const int16_t* coef, int32_t n, int32_t H, int32_t W, const uint8_t* header, int32_t header_len,
+                          void* scratch, int64_t scratch_bytes, uint8_t* out, int64_t out_cap, int64_t* offsets, int64_t* needed,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,9 @@ _SIGNATURES = {
     "sdv_clip_preprocess_patches": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 +
                                     [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
     "sdv_safety_screen": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdv_jpeg_transform_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.c_void_p, C.c_void_p]),
+    "sdv_jpeg_entropy_pack": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1159,3 +1162,81 @@ def safety_screen(image_embeds: torch.Tensor, concept: torch.Tensor, special: to
     scores = torch.empty((n, special.shape[0] + concept.shape[0]), dtype=F32, device=image_embeds.device)
     _k_safety_screen(image_embeds, concept, special, thr_c, thr_s, frames, flags, scores)
     return flags, scores
+
+
+# ------------------------------------------------------------------------------------------------
+# JPEG encoder (csrc/sdv_jpeg.hip; jpeg.py builds the tables, the header and the workspaces)
+# ------------------------------------------------------------------------------------------------
+def jpeg_mcu_grid(H: int, W: int):
+    return (H + 15) // 16, (W + 15) // 16
+
+
+def jpeg_scratch_bytes(n: int, H: int) -> int:
+    """sdv_jpeg_entropy_pack's scratch: an int64 position and an int32 length per restart interval (one per MCU row and frame)."""
+    return 12 * n * ((H + 15) // 16)
+
+
+def _jpeg_transform_impl(frames, qtab_luma, qtab_chroma, coef):
+    if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise SdvHipError(f"jpeg_transform: frames must be a contiguous uint8 [n, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)} "
+                          f"contiguous={frames.is_contiguous()}")
+    n, H, W, _ = frames.shape
+    rows, cols = jpeg_mcu_grid(H, W)
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, rows, cols, 6, 64) or not coef.is_contiguous():
+        raise SdvHipError(f"jpeg_transform: coef must be a contiguous int16 [{n}, {rows}, {cols}, 6, 64] tensor, got {coef.dtype} {tuple(coef.shape)}")
+    if len(qtab_luma) != 64 or len(qtab_chroma) != 64:
+        raise SdvHipError(f"jpeg_transform: quantisation tables hold 64 entries, got {len(qtab_luma)} / {len(qtab_chroma)}")
+    if any(not 0 <= int(v) <= 65535 for v in list(qtab_luma) + list(qtab_chroma)):
+        raise SdvHipError("jpeg_transform: quantisation table entry outside 1 .. 255")
+    lib = load()
+    ql, qc = (C.c_uint16 * 64)(*[int(v) for v in qtab_luma]), (C.c_uint16 * 64)(*[int(v) for v in qtab_chroma])
+    args = (_ptr(frames, name="frames"), n, H, W, ql, qc, _ptr(coef, name="coef"))
+    _launch("jpeg_transform", dict(bytes=3.0 * n * H * W + 2.0 * coef.numel()),
+            lambda: _check(lib.sdv_jpeg_transform_u8(*args, _stream()), "sdv_jpeg_transform_u8"))
+
+
+_k_jpeg_transform = _defop("k_jpeg_transform(Tensor frames, int[] qtab_luma, int[] qtab_chroma, Tensor(a!) coef) -> ()", _jpeg_transform_impl)
+
+
+def jpeg_transform(frames: torch.Tensor, qtab_luma, qtab_chroma, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 RGB frames [n, H, W, 3] in HBM -> quantised DCT coefficients int16 [n, ceil(H/16), ceil(W/16), 6, 64], zigzag order, MCU
+    block order Y00 Y01 Y10 Y11 Cb Cr (``torch.ops.sdv.k_jpeg_transform`` -> sdv_jpeg_transform_u8).  Tables: 64 entries, natural order."""
+    if out is None:
+        rows, cols = jpeg_mcu_grid(frames.shape[1], frames.shape[2])
+        out = torch.empty((frames.shape[0], rows, cols, 6, 64), dtype=torch.int16, device=frames.device)
+    _k_jpeg_transform(frames, [int(v) for v in qtab_luma], [int(v) for v in qtab_chroma], out)
+    return out
+
+
+def _jpeg_entropy_pack_impl(coef, H, W, header, scratch, out, offsets, needed):
+    rows, cols = jpeg_mcu_grid(H, W)
+    if coef.dtype != torch.int16 or coef.ndim != 5 or tuple(coef.shape[1:]) != (rows, cols, 6, 64) or not coef.is_contiguous():
+        raise SdvHipError(f"jpeg_entropy_pack: coef must be a contiguous int16 [n, {rows}, {cols}, 6, 64] tensor for {H} x {W} frames, got "
+                          f"{coef.dtype} {tuple(coef.shape)}")
+    n = coef.shape[0]
+    for name, t in (("header", header), ("scratch", scratch), ("out", out)):
+        if t.dtype != torch.uint8 or t.ndim != 1 or not t.is_contiguous():
+            raise SdvHipError(f"jpeg_entropy_pack: {name} must be a contiguous 1-D uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+    if scratch.numel() < jpeg_scratch_bytes(n, H):
+        raise SdvHipError(f"jpeg_entropy_pack: scratch holds {scratch.numel()} bytes, {n} frames of {rows} MCU rows need {jpeg_scratch_bytes(n, H)}")
+    if offsets.dtype != torch.int64 or offsets.numel() != n + 1 or not offsets.is_contiguous():
+        raise SdvHipError(f"jpeg_entropy_pack: offsets must be a contiguous int64 vector of n + 1 = {n + 1} elements, got {offsets.dtype} x {offsets.numel()}")
+    if needed.dtype != torch.int64 or needed.numel() != 1:
+        raise SdvHipError(f"jpeg_entropy_pack: needed must be one int64 element, got {needed.dtype} x {needed.numel()}")
+    lib = load()
+    args = (_ptr(coef, name="coef"), n, H, W, _ptr(header, name="header"), header.numel(), _ptr(scratch, name="scratch"), scratch.numel(),
+            _ptr(out, name="out"), out.numel(), _ptr(offsets, name="offsets"), _ptr(needed, name="needed"))
+    _launch("jpeg_entropy_pack", dict(bytes=2.0 * 2 * coef.numel()),
+            lambda: _check(lib.sdv_jpeg_entropy_pack(*args, _stream()), "sdv_jpeg_entropy_pack"))
+
+
+_k_jpeg_entropy_pack = _defop("k_jpeg_entropy_pack(Tensor coef, int H, int W, Tensor header, Tensor(a!) scratch, Tensor(b!) out, Tensor(c!) offsets, "
+                              "Tensor(d!) needed) -> ()", _jpeg_entropy_pack_impl)
+
+
+def jpeg_entropy_pack(coef: torch.Tensor, H: int, W: int, header: torch.Tensor, scratch: torch.Tensor, out: torch.Tensor,
+                      offsets: torch.Tensor, needed: torch.Tensor):
+    """Huffman-code the coefficient blocks and pack complete files into ``out`` (``torch.ops.sdv.k_jpeg_entropy_pack`` ->
+    sdv_jpeg_entropy_pack): ``out[offsets[k]:offsets[k + 1]]`` is file k.  When ``needed`` (= offsets[n]) exceeds ``out.numel()``
+    nothing was written to ``out``: call again with a buffer of that size."""
+    _k_jpeg_entropy_pack(coef, int(H), int(W), header, scratch, out, offsets, needed)

@@ -116,6 +116,7 @@ class StableDiffusionWalkPipeline:
         self.vae_scale_factor = 2 ** (len(self.vae.config.block_out_channels) - 1)      # :158
         self.tiled = False
         self.upsampler = None
+        self.jpeg_quality = 75             # output_type="jpeg" and .jpg / .jpeg frame files (what PIL's Image.save writes for them)
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
@@ -669,8 +670,9 @@ class StableDiffusionWalkPipeline:
                 callback(i, self.scheduler.timesteps[i].item(), hip.nhwc_to_nchw(ent["latents"]))
         if kwargs.get("return_latents", False):
             return hip.nhwc_to_nchw(ent["latents"])[:B_real]
-        # "numpy_u8": rounded uint8 NHWC array, no PIL objects; "u8_cuda": the same array left in HBM (upsampler input)
-        want_float = output_type not in ("pil", "numpy_u8", "u8_cuda")
+        # "numpy_u8": rounded uint8 NHWC array, no PIL objects; "u8_cuda": the same array left in HBM (upsampler input);
+        # "jpeg": list[bytes], each a complete JFIF file compressed on the GPU (jpeg.py) - only compressed bytes cross to the host
+        want_float = output_type not in ("pil", "numpy_u8", "u8_cuda", "jpeg")
         u8, f32 = self.vae.decode(ent["latents"], want_float=want_float)                         # :432-435
         flags_host = None
         if self.safety_checker is not None:                                                       # :440-447
@@ -684,6 +686,9 @@ class StableDiffusionWalkPipeline:
             flags_host.copy_(flags_dev, non_blocking=True)
         if output_type == "u8_cuda":
             image = u8[:B_real]
+        elif output_type == "jpeg":                                                               # (after the black-out above)
+            from .jpeg import encoder_for
+            image = encoder_for(self.jpeg_quality, u8.device).encode(u8[:B_real])
         elif want_float:
             image = f32[:B_real].cpu().numpy()                                                    # :438
         else:
@@ -763,6 +768,9 @@ class StableDiffusionWalkPipeline:
         num_batches = math.ceil(num_interpolation_steps / batch_size)
         log_prefix = "" if step is None else f"[{step[0]}/{step[1]}] "
         writer = self._writer or FrameWriter()
+        # .jpg / .jpeg frames are compressed on the GPU at the quality and subsampling Image.save uses for these extensions (75, 4:2:0);
+        # SDV_JPEG=pil keeps the host-side PIL encode.  Every other extension is untouched.
+        gpu_jpeg = image_file_ext.lower() in (".jpg", ".jpeg") and os.environ.get("SDV_JPEG", "hip").lower() != "pil"
         pos = 0
         for batch_idx, embeds_batch, noise_batch in batch_generator:
             frame_index = indices[pos]
@@ -773,7 +781,15 @@ class StableDiffusionWalkPipeline:
             logger.info(f"{log_prefix}[{batch_idx}/{num_batches}] {msg}")
             outputs = self(latents=noise_batch, text_embeddings=embeds_batch, height=height, width=width,
                            guidance_scale=guidance_scale, eta=eta, num_inference_steps=num_inference_steps,
-                           output_type="pil" if not upsample else "u8_cuda", negative_prompt=negative_prompt)["images"]
+                           output_type="u8_cuda" if (upsample or gpu_jpeg) else "pil", negative_prompt=negative_prompt)["images"]
+            if gpu_jpeg:
+                from .jpeg import encoder_for
+                if upsample:
+                    outputs = self.upsampler.upsample_u8(outputs)
+                for data in encoder_for(self.jpeg_quality, outputs.device).encode(outputs):
+                    writer.submit_bytes(data, save_path / (f"frame%06d{image_file_ext}" % indices[pos]))
+                    pos += 1
+                continue
             if upsample:
                 # :552 - the reference upsamples frame by frame on the way to disk (float -> uint8 -> RealESRGANer); here the
                 # uint8 frames never leave HBM before the x4 network has run on the whole batch
@@ -924,7 +940,8 @@ class StableDiffusionWalkPipeline:
                     eta=eta, height=height, width=width, upsample=upsample, batch_size=batch_size,
                     T=get_timesteps_arr(audio_filepath, offset=audio_offset, duration=audio_duration, fps=fps,
                                         margin=margin, smooth=smooth) if audio_filepath else None,
-                    frame_indices=frames, negative_prompt=negative_prompt, step=(i, len(prompts) - 1))
+                    frame_indices=frames, negative_prompt=negative_prompt, step=(i, len(prompts) - 1),
+                    image_file_ext=image_file_ext)       # (the reference drops it here and always writes .png frames, :758)
         finally:
             self._writer.close()
             self._writer = None

@@ -85,6 +85,17 @@ class FrameWriter:
     def submit(self, image, path: Path, upsampler=None):
         self.pending.append(self.pool.submit(self._save, image, path, upsampler))
 
+    @staticmethod
+    def _save_bytes(data: bytes, path: Path):
+        path = Path(path)
+        tmp = path.with_name(path.name + ".part")
+        tmp.write_bytes(data)
+        os.replace(tmp, path)
+
+    def submit_bytes(self, data: bytes, path: Path):
+        """A frame that is already an encoded file (jpeg.py: compressed on the GPU): same ``.part``-then-rename rule as ``submit``."""
+        self.pending.append(self.pool.submit(self._save_bytes, data, path))
+
     def drain(self):
         pending, self.pending = self.pending, []
         for f in pending:

@@ -207,15 +207,24 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
                     output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png"):
     """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it."""
     output_filepath = str(output_filepath)
-    frames = _frames_uint8(frames_or_frame_dir, glob_pattern)
-    if not frames:
+    gpu_frames = None                      # a uint8 tensor in GPU memory: a Motion-JPEG track is compressed there (jpeg.py)
+    if isinstance(frames_or_frame_dir, torch.Tensor) and frames_or_frame_dir.is_cuda and frames_or_frame_dir.dtype == torch.uint8 \
+            and frames_or_frame_dir.ndim == 4 and frames_or_frame_dir.shape[0] > 0:
+        t = frames_or_frame_dir
+        gpu_frames = t.permute(0, 2, 3, 1) if t.shape[1] in (1, 3) else t
+        if gpu_frames.shape[-1] != 3:
+            gpu_frames = None
+    # (the raw frames of such a tensor are copied to the host only by the encoders that need them there)
+    frames = _frames_uint8(frames_or_frame_dir, glob_pattern) if gpu_frames is None else None
+    n_frames = len(frames) if frames is not None else int(gpu_frames.shape[0])
+    if not n_frames:
         raise ValueError(f"no frames found for {frames_or_frame_dir} / {glob_pattern}")
     try:
         from torchvision.io import write_video
     except Exception:
         write_video = None
     if write_video is not None:                                                           # reference encoding
-        stack = torch.from_numpy(np.stack(frames))
+        stack = torch.from_numpy(np.stack(frames if frames is not None else _frames_uint8(frames_or_frame_dir, glob_pattern)))
         if audio_filepath:
             from .audio import load_audio
             audio, _ = load_audio(audio_filepath, sr=sr, mono=True, offset=audio_offset, duration=audio_duration)
@@ -231,17 +240,17 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     codec = (os.environ.get("SDV_VIDEO_CODEC") or DEFAULT_CODEC).lower()
     if codec not in ("h264", "mjpeg"):
         raise ValueError(f"SDV_VIDEO_CODEC={codec!r}: expected 'h264' or 'mjpeg'")
-    h, w = frames[0].shape[:2]
+    h, w = frames[0].shape[:2] if frames is not None else (int(gpu_frames.shape[1]), int(gpu_frames.shape[2]))
     if codec == "h264":
-        est = len(frames) * (w * h * 3 // 2)
+        est = n_frames * (w * h * 3 // 2)
         if est > H264_PCM_MAX_BYTES and not os.environ.get("SDV_VIDEO_CODEC"):
             logger.warning("%d frames of %dx%d as uncompressed I_PCM H.264 would be %.1f GB: writing Motion-JPEG instead "
-                           "(set SDV_VIDEO_CODEC=h264 to force, SDV_H264_PCM_MAX_BYTES to move the limit)", len(frames), w, h, est / 1e9)
+                           "(set SDV_VIDEO_CODEC=h264 to force, SDV_H264_PCM_MAX_BYTES to move the limit)", n_frames, w, h, est / 1e9)
             codec = "mjpeg"
             why = f"estimated I_PCM stream {est} bytes > {H264_PCM_MAX_BYTES}"
         else:
             logger.info("H.264 I_PCM video track: %d frames of %dx%d = %.1f MB (uncompressed, 1.5 bytes per pixel)",
-                        len(frames), w, h, est / 1e6)
+                        n_frames, w, h, est / 1e6)
     if codec == "h264" and (h % 2 or w % 2):
         logger.warning("odd frame size %dx%d: yuv420p needs even sizes, writing Motion-JPEG instead", w, h)
         codec = "mjpeg"
@@ -254,7 +263,14 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     LAST_CODEC.update(path=output_filepath, video="h264 (I_PCM)" if codec == "h264" else "mjpeg", audio="pcm_s16le" if audio is not None else None,
                       why=why)
     if codec == "h264":
-        return write_h264_mp4(frames, w, h, fps, output_filepath, audio=audio, sr=sr)
+        return write_h264_mp4(frames if frames is not None else _frames_uint8(frames_or_frame_dir, glob_pattern), w, h, fps, output_filepath,
+                              audio=audio, sr=sr)
+    if gpu_frames is not None:
+        from .jpeg import encoder_for
+        enc = encoder_for(95, gpu_frames.device)
+        step = max(1, (64 << 20) // (h * w * 3))                                            # batches of about 64 MB of raw frames
+        jpegs = [j for k in range(0, gpu_frames.shape[0], step) for j in enc.encode(gpu_frames[k:k + step].contiguous())]
+        return write_mjpeg_mp4(jpegs, w, h, fps, output_filepath, audio=audio, sr=sr)
     from PIL import Image
     jpegs = []
     for fr in frames:
