@@ -41,6 +41,7 @@ from . import config as cfgs
 from . import hip, parallel, weights
 from .engine import UNetEngine, VAEDecoderEngine
 from .scheduler import DDIMScheduler, adopt as adopt_scheduler
+from .step_graphs import DenoiseStep, StepGraphCache, StepKey
 from .text import build_text_encoder, load_tokenizer
 from .utils import FrameWriter, get_timesteps_arr, make_video_pyav, numpy_to_pil
 from .vision import SafetyCheckerEngine
@@ -48,7 +49,6 @@ from .vision import SafetyCheckerEngine
 logger = logging.getLogger("stable_diffusion_videos_amd")
 
 F32 = torch.float32
-BF16 = torch.bfloat16
 
 
 class StableDiffusionPipelineOutput(dict):
@@ -122,9 +122,9 @@ class StableDiffusionWalkPipeline:
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
         self.cfg_shared_prefix = os.environ.get("SDV_NO_CFG_SHARED", "0") != "1"   # see UNetEngine.forward
         self._device = torch.device("cpu")
-        self._graphs: Dict[tuple, dict] = {}
-        self._graph_pool = None            # the private memory pool every captured step allocates from (see _capture)
-        self.max_cached_graphs = 4         # LRU bound on captured denoise-step graphs (all share ONE private pool, which only shrinks when every graph is dropped)
+        # captured denoise steps (step_graphs.py); it frees through the engine's bound method, not through this object, so the
+        # pipeline stays out of any reference cycle - ``to()`` points it at the engine it builds
+        self._graphs = StepGraphCache(release=getattr(unet, "release", None))
         self._uncond_cache: Dict[str, torch.Tensor] = {}
         self._sched_cache: Dict[tuple, tuple] = {}
         self._writer: Optional[FrameWriter] = None
@@ -255,6 +255,7 @@ class StableDiffusionWalkPipeline:
             u_shapes = weights.unet_shapes(u.config)
             u_sd = parallel.broadcast_state_dict(u.state_dict, u_shapes, device)
             self.unet = UNetEngine(u.config, u_sd, device, tiled=self.tiled, fp8=getattr(self, "fp8", False))
+            self._graphs.release = self.unet.release      # whatever replaces self.unet must re-point this: the cache frees through it
             del u_sd
             u.state_dict = None
             if isinstance(v, _PendingModule):
@@ -272,6 +273,19 @@ class StableDiffusionWalkPipeline:
     @property
     def device(self) -> torch.device:
         return self._device
+
+    @property
+    def max_cached_graphs(self) -> int:
+        """LRU bound on cached denoise steps (default 4)."""
+        return self._graphs.bound
+
+    @max_cached_graphs.setter
+    def max_cached_graphs(self, n: int):
+        self._graphs.bound = n
+
+    @property
+    def last_graph_build(self) -> Dict[str, float]:
+        return self._graphs.last_build
 
     def enable_attention_slicing(self, slice_size: Optional[Union[str, int]] = "auto"):
         """Accepted for API compatibility (reference :161-181).  The HIP attention kernel is flash-style and
@@ -347,10 +361,7 @@ class StableDiffusionWalkPipeline:
             while len(self._sched_cache) >= 8:
                 gone = next(iter(self._sched_cache))
                 self._sched_cache.pop(gone)
-                # captured steps bake in the pointers of that schedule's coefficient / time-embedding tables
-                for gk in [k for k in self._graphs if k[0] == gone]:
-                    dead = self._graphs.pop(gk)
-                    dead["graph"] = dead["one_step"] = None
+                self._graphs.drop_schedule(gone)
             coefs = (self.scheduler.coefficient_table(eta) if ddim else self.scheduler.fused_table()).to(self.device)
             self.unet.prepare_timesteps(ts)
             tables = [r.bias_table for r in self.unet.res]
@@ -377,12 +388,7 @@ class StableDiffusionWalkPipeline:
     def _drop_graphs(self):
         """Forget every captured step the way the LRU eviction does: the graph object goes, and so do the per-batch-size
         cross-attention buffers it held raw pointers into."""
-        sizes = {k[1] for k in self._graphs}
-        for ent in self._graphs.values():
-            ent["graph"] = ent["one_step"] = None        # (the closure holds the entry: break the cycle, the buffers go now)
         self._graphs.clear()
-        for nimg in sizes:
-            self.unet.release(nimg)
 
     def fp8_saturated(self) -> int:
         """Clamped e4m3 conversions since ``enable_fp8_saturation_check()`` (host synchronising)."""
@@ -412,24 +418,16 @@ class StableDiffusionWalkPipeline:
         else:
             pilot_ctx = torch.cat([uncond] * nimg)
         self.unet.prepare_context(pilot_ctx)
-        self.unet.reserve(nimg, h, w)
-        x2 = torch.zeros((nimg * h * w, C), dtype=BF16, device=self.device)
-        step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # (no noise: a stochastic scheduler's noise term is left out of the pilot, it only widens the scales)
+        pilot = DenoiseStep(self.unet, 1, h, w, cfg, cfg and self.cfg_shared_prefix, guidance, coefs)
+        pilot.latents = lat                # (stepped in place)
         s0 = self.scheduler.first_input_scale() if hasattr(self.scheduler, "first_input_scale") else 1.0
-        hip.latents_to_unet_input(lat if s0 == 1.0 else lat * s0, x2, cfg, lat.numel())
-        multistep = coefs.shape[1] == 16
-        hist = torch.zeros((4,) + tuple(lat.shape), dtype=F32, device=self.device) if multistep else None
-        xsave = torch.zeros_like(lat) if multistep else None
+        hip.latents_to_unet_input(lat if s0 == 1.0 else lat * s0, pilot.x2, cfg, lat.numel())
         before = self.unet.fp8_scales()
         self.unet.fp8_calibration(True)
         try:
             for _ in range(nsteps):
-                eps = self.unet.forward(x2, nimg, h, w, step, cfg_shared=cfg and self.cfg_shared_prefix)
-                if multistep:      # (a stochastic scheduler's noise term is left out of the pilot: it only widens the scales)
-                    hip.cfg_multistep_step(eps, lat, x2, hist, xsave, coefs, step, None, guidance, cfg, lat.numel())
-                else:
-                    hip.cfg_ddim_step(eps, lat, x2, coefs, step, None, guidance, cfg, lat.numel())
-                hip.step_counter_add(step, 1)
+                pilot.body()
             torch.cuda.synchronize(self.device)
         except BaseException:
             # a pilot that died part-way (out of memory, a bad shape) must not leave half-widened scales behind and must not
@@ -438,110 +436,8 @@ class StableDiffusionWalkPipeline:
             raise
         self.unet.fp8_calibration(False)
         # the pilot's 2-sample cross-attention K / V^T buffers and workspaces are only kept when a 2-sample step is what runs next
-        if not any(k[1] == nimg for k in self._graphs):
+        if not self._graphs.holds(nimg):
             self.unet.release(nimg)
-
-    def _graph_entry(self, key: tuple, nimg: int, B: int, h: int, w: int, cfg: bool, guidance: float, coefs, eta_noise):
-        """Static buffers + a captured hipGraph of ONE denoise step (UNet forward + CFG/DDIM update + step++)."""
-        if key in self._graphs:
-            ent = self._graphs[key] = self._graphs.pop(key)    # most recently used last
-            # an entry made while use_graphs was off (or whose capture failed) is captured behind its next eager step once graphs
-            # are on again - otherwise it would run eagerly for ever (ADVICE r5)
-            if self.use_graphs and ent["graph"] is None and not ent.get("capture_failed"):
-                ent["capture_pending"] = True
-            return ent
-        while len(self._graphs) >= self.max_cached_graphs:     # bound the static buffers + cross-attention K / V^T sets kept alive
-            old_key = next(iter(self._graphs))
-            ent = self._graphs.pop(old_key)
-            ent["graph"] = ent["one_step"] = None
-            del ent
-            # the cross-attention K / V^T buffers of the text context are kept per batch size because captured graphs hold raw
-            # pointers into them: once no cached graph runs at that batch size any more they go too (a resumed walk with many
-            # short runs would otherwise leave one set per distinct batch size behind)
-            if not any(k[1] == old_key[1] for k in self._graphs) and old_key[1] != nimg:
-                self.unet.release(old_key[1])
-        dev = self.device
-        C = self.unet.cfg.in_channels
-        ent = {
-            "latents": torch.zeros((B, h, w, C), dtype=F32, device=dev),
-            "x2": torch.zeros((nimg * h * w, C), dtype=BF16, device=dev),
-            "step": torch.zeros(1, dtype=torch.int32, device=dev),
-            "graph": None,
-        }
-        self.unet.reserve(nimg, h, w)
-        n = B * h * w * C
-        multistep = coefs.shape[1] == 16           # sdv_cfg_multistep_step rows (every scheduler but DDIM)
-        if multistep:
-            ent["hist"] = torch.zeros((4, B, h, w, C), dtype=F32, device=dev)      # ring of earlier model outputs
-            ent["xsave"] = torch.zeros((B, h, w, C), dtype=F32, device=dev)        # PLMS: the sample of the first evaluation
-
-        def one_step():
-            eps = self.unet.forward(ent["x2"], nimg, h, w, ent["step"], cfg_shared=cfg and self.cfg_shared_prefix)
-            if multistep:
-                hip.cfg_multistep_step(eps, ent["latents"], ent["x2"], ent["hist"], ent["xsave"], coefs, ent["step"], eta_noise,
-                                       guidance, cfg, n)
-            else:
-                hip.cfg_ddim_step(eps, ent["latents"], ent["x2"], coefs, ent["step"], eta_noise, guidance, cfg, n)
-            hip.step_counter_add(ent["step"], 1)
-
-        ent["one_step"] = one_step
-        # The step is captured by ``_capture`` right AFTER its first eager execution - which is the first REAL denoise step of the
-        # first call at this key (lazy allocations / attribute sets happen there), not a throw-away warm-up on zero-filled buffers.
-        ent["capture_pending"] = bool(self.use_graphs)
-        self._graphs[key] = ent
-        return ent
-
-    def _capture(self, ent: dict):
-        """Capture ``ent``'s denoise step into a hipGraph (nothing executes: the static buffers keep the state the eager step
-        left).  Not through the ``torch.cuda.graph`` context manager: its ``__enter__`` runs ``torch.cuda.empty_cache()``, which
-        hands every cached block of the allocator back to the driver - 0.9 s for a 16-frame capture that followed a 60-frame call,
-        1.7 s of the 2.15 s "cold start" the round-4 bench line showed (profiles/round5_cold_start_probe_before.txt); the capture
-        itself is 14 ms.  All captured steps share ONE private memory pool: their intermediates are dead when a replay ends and
-        two steps never run concurrently, so a new batch size costs the pool only what it needs beyond the largest so far."""
-        t0 = time.perf_counter()
-        dev = self.device
-        # The shared pool lives as long as one graph captured into it does: once every captured step has been dropped (fp8 counter
-        # switch, LRU eviction of the last one, a caller clearing ``_graphs``) PyTorch forgets the pool, and capturing into the stale
-        # handle trips an internal assert of its caching allocator (seen when the collector had already freed the old graphs).
-        if self._graph_pool is None or not any(e.get("graph") is not None for e in self._graphs.values()):
-            self._graph_pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        # with a process group alive its watchdog thread may touch the runtime while this thread captures: only this
-        # thread's calls (kernel launches through the C ABI) need to be capture-safe
-        mode = "thread_local" if parallel.world()[1] > 1 else "global"
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        # No garbage collection while the stream captures: an unreachable step graph of an earlier call (its entry holds a closure
-        # that holds the entry - a cycle only the collector frees) would be destroyed in the middle of the capture, and destroying
-        # a graph / returning its blocks is not a capturable call (seen as a crash inside the first captured launch when this ran
-        # late in a long test session; ``torch.cuda.graph`` runs a full ``gc.collect()`` up front for the same reason - switching
-        # the collector off for the ~10 ms of the capture costs nothing).
-        import gc
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        ent["capture_pending"] = False          # whatever happens below, the capture is not retried on every following step
-        err = None
-        try:
-            with torch.cuda.stream(side):
-                g.capture_begin(pool=self._graph_pool, capture_error_mode=mode)
-                try:
-                    ent["one_step"]()
-                except BaseException as e:      # keep the ORIGINAL error: capture_end() on a broken capture raises one of its own
-                    err = e
-                try:
-                    g.capture_end()
-                except BaseException as e:
-                    if err is None:
-                        err = e
-        finally:
-            if gc_was_on:
-                gc.enable()
-            torch.cuda.current_stream().wait_stream(side)
-        if err is not None:
-            ent["capture_failed"] = True        # this entry keeps running eagerly
-            raise err
-        ent["graph"] = g
-        self.last_graph_build = {"capture_s": time.perf_counter() - t0}
 
     @torch.no_grad()
     def __call__(self, prompt: Optional[Union[str, List[str]]] = None, height: Optional[int] = None,
@@ -617,63 +513,51 @@ class StableDiffusionWalkPipeline:
             pilot_cond = getattr(self, "_fp8_pilot_cond", None)
             self._calibrate_fp8(h, w, coefs, nsteps, float(guidance_scale), do_cfg,
                                 cond=pilot_cond if pilot_cond is not None else text_embeddings[:1])
-        # A ragged last batch (B frames where a graph for B' > B frames is already captured) is padded with copies of its
-        # last frame and replays the big graph: a second capture would own a second multi-GB private pool for one call.
-        # Only while the padding is at most a quarter of the big batch - 60 frames replayed as 128 would pay for 128.
         B_real = B
+        mult = 2 if do_cfg else 1
+        stochastic = (eta > 0 and hasattr(self.scheduler, "coefficient_table")) or getattr(self.scheduler, "stochastic", False)
+        gkey = StepKey(sched_key, mult * B, h, w, do_cfg, float(guidance_scale), stochastic, int(ctx.shape[1]),
+                       self.cfg_shared_prefix, self.tiled)
         if self.use_graphs and eta == 0 and callback is None and not getattr(self.scheduler, "stochastic", False):
-            tail = (h, w, do_cfg, float(guidance_scale), False, int(ctx.shape[1]), self.cfg_shared_prefix, self.tiled)
-            mult = 2 if do_cfg else 1
-            bigger = [k[1] // mult for k in self._graphs if k[0] == sched_key and k[2:] == tail and k[1] // mult > B]
-            if bigger and 4 * (min(bigger) - B) <= min(bigger) and \
-                    (B * mult, ) + tail not in {k[1:] for k in self._graphs if k[0] == sched_key}:
-                pad = min(bigger) - B
+            # a ragged last batch is padded with copies of its last frame and replays the bigger captured step (padded_batch)
+            padded = self._graphs.padded_batch(gkey, B)
+            if padded is not None:
+                pad = padded - B
                 latents = torch.cat([latents, latents[-1:].expand(pad, -1, -1, -1)])
                 if do_cfg:
                     u, c = ctx[:B], ctx[B:]
                     ctx = torch.cat([u, u[-1:].expand(pad, -1, -1), c, c[-1:].expand(pad, -1, -1)])
                 else:
                     ctx = torch.cat([ctx, ctx[-1:].expand(pad, -1, -1)])
-                B += pad
-        nimg = 2 * B if do_cfg else B
+                B = padded
+                gkey = gkey._replace(nimg=mult * B)
         eta_noise = None
-        stochastic = (eta > 0 and hasattr(self.scheduler, "coefficient_table")) or getattr(self.scheduler, "stochastic", False)
         if stochastic:
             gdev = generator.device if generator is not None else torch.device("cpu")
             eta_noise = torch.randn((nsteps, B, h, w, C), generator=generator, device=gdev, dtype=F32).to(self.device)
         self.unet.prepare_context(ctx)
-        # everything a captured step bakes in: pointers of the (nimg, Lc) cross-attention K/V buffers, the shared-prefix
-        # structure, padding mode, guidance scale, schedule
-        gkey = (sched_key, nimg, h, w, do_cfg, float(guidance_scale), stochastic, int(ctx.shape[1]), self.cfg_shared_prefix,
-                self.tiled)
-        ent = self._graph_entry(gkey, nimg, B, h, w, do_cfg, float(guidance_scale), coefs, eta_noise)
-        if stochastic:
-            ent.setdefault("noise", eta_noise)
-            if ent["noise"] is not eta_noise:
-                ent["noise"].copy_(eta_noise)
+        ent = self._graphs.step(gkey, lambda: DenoiseStep(self.unet, B, h, w, do_cfg, do_cfg and self.cfg_shared_prefix,
+                                                          float(guidance_scale), coefs, eta_noise), capture=self.use_graphs)
+        if stochastic and ent.noise is not eta_noise:
+            ent.noise.copy_(eta_noise)
 
         lat_nhwc = hip.nchw_to_nhwc(latents * self.scheduler.init_noise_sigma)                    # :401
-        ent["latents"].copy_(lat_nhwc)
-        ent["step"].zero_()
+        ent.latents.copy_(lat_nhwc)
+        ent.step.zero_()
         s0 = self.scheduler.first_input_scale() if hasattr(self.scheduler, "first_input_scale") else 1.0
         # :414-415: torch.cat([latents] * 2) -> scheduler.scale_model_input (sigma-space schedulers: x / sqrt(sigma_0^2 + 1))
-        hip.latents_to_unet_input(ent["latents"] if s0 == 1.0 else ent["latents"] * s0, ent["x2"], do_cfg, ent["latents"].numel())
+        hip.latents_to_unet_input(ent.latents if s0 == 1.0 else ent.latents * s0, ent.x2, do_cfg, ent.latents.numel())
         t_prep = time.perf_counter()
         for i in range(nsteps):                                                                   # :412
-            if ent["graph"] is not None:
-                ent["graph"].replay()
-            else:
-                ent["one_step"]()
-                if ent.get("capture_pending"):
-                    self._capture(ent)
+            self._graphs.run(ent)
             if callback is not None and i % callback_steps == 0:                                  # :429
-                callback(i, self.scheduler.timesteps[i].item(), hip.nhwc_to_nchw(ent["latents"]))
+                callback(i, self.scheduler.timesteps[i].item(), hip.nhwc_to_nchw(ent.latents))
         if kwargs.get("return_latents", False):
-            return hip.nhwc_to_nchw(ent["latents"])[:B_real]
+            return hip.nhwc_to_nchw(ent.latents)[:B_real]
         # "numpy_u8": rounded uint8 NHWC array, no PIL objects; "u8_cuda": the same array left in HBM (upsampler input);
         # "jpeg": list[bytes], each a complete JFIF file compressed on the GPU (jpeg.py) - only compressed bytes cross to the host
         want_float = output_type not in ("pil", "numpy_u8", "u8_cuda", "jpeg")
-        u8, f32 = self.vae.decode(ent["latents"], want_float=want_float)                         # :432-435
+        u8, f32 = self.vae.decode(ent.latents, want_float=want_float)                            # :432-435
         flags_host = None
         if self.safety_checker is not None:                                                       # :440-447
             # on the uint8 frames in HBM, before they leave it: flagged frames go out already black, and the flags ride on the same

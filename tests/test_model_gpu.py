@@ -728,6 +728,37 @@ def test_ragged_last_batch_reuses_the_captured_graph(hip, dev, tmp_path):
     assert len(pipe2._graphs) == 2                    # 4 frames + a 1-frame tail with its own captured step
 
 
+def test_graph_cache_evicts_releases_and_recaptures(hip, dev):
+    """The step cache beyond its happy path, with room for 2 steps: batch sizes 1, 2, 3, 1 - the third call evicts the 1-frame
+    step and releases its cross-attention K / V^T buffers, the fourth captures again at that size into fresh ones - and a step
+    first run with graphs off that is captured once they are on.  Every call equals the same call of an eager pipeline bit for
+    bit (tiny arch, 64 x 64, 3 DDIM steps, CFG 7.5)."""
+    pipe, eager = _tiny_pipeline(dev), _tiny_pipeline(dev)
+    eager.use_graphs = False
+    pipe.max_cached_graphs = 2
+    emb = pipe.embed_text(["a cat", "a dog", "a horse", "a cow"]).cpu()
+    lat = torch.cat([pipe.init_noise(s, (1, 4, 8, 8)) for s in (42, 1337, 7, 11)]).cpu()
+
+    def run(p, B):
+        return p(latents=lat[:B], text_embeddings=emb[:B], height=64, width=64, num_inference_steps=3, guidance_scale=7.5,
+                 output_type="numpy_u8")["images"]
+
+    def newest(p):
+        return list(p._graphs)[-1]
+
+    for call, B in enumerate((1, 2, 3, 1)):
+        assert np.array_equal(run(pipe, B), run(eager, B)), (call, B)
+        assert newest(pipe).graph is not None and len(pipe._graphs) == min(call + 1, 2)
+        if call == 2:       # steps of 2 and 3 frames (4 and 6 samples) are cached: the 2-sample buffers of the first call are gone
+            assert {k[0] for k in pipe.unet.tfm[0].ctx_by_len} <= {4, 6}
+    pipe.use_graphs = False
+    off = run(pipe, 4)
+    assert newest(pipe).graph is None and np.array_equal(off, run(eager, 4))
+    pipe.use_graphs = True
+    on = run(pipe, 4)
+    assert np.array_equal(on, off) and newest(pipe).graph is not None
+
+
 def test_walk_with_audio_and_video(hip, dev, tmp_path):
     """Mirror of the reference's test_walk_with_audio (tests/test_pipeline.py:53-68): audio-driven T per clip,
     batch_size 16, and the mp4 files of the documented layout (:648-666) exist."""
