@@ -161,74 +161,130 @@ class _Res:
         return hip.conv3x3(h, self.w2, self.c2_bias, nimg=nimg, H=H, W=W, residual=sc, circular=circular, out=out, gn=True)
 
 
+class _Proj:
+    """One token projection of the transformer block,  y = alpha (LN?(x) W^T) + b (+ residual) (+ the row statistics of y),  with its
+    weights in the operand format of each kernel that can run it: the igemm tiles (hip.linear) and, where the panel kernel has a form
+    for its width (hip.linear320: C = 320, and C = 640 without a residual), that one.  Which of the two runs is decided here and
+    nowhere else, so a caller cannot pair one kernel's weights with the other's fold terms."""
+
+    def __init__(self, parts, bias, device, ln=None, panel_widths=()):
+        """``parts``: [(weight [N_i, C], alpha_i)], stacked along N; alpha_i multiplies those output columns (the pre-scale of a Q
+        projection; only the first may differ from 1).  ``ln``: (gamma, beta) of the LayerNorm that feeds the projection, folded into
+        it (weights.ln_fold / sdv_hip.h ln_side): the GEMM that PRODUCES x also emits its row statistics, this one reads the
+        un-normalised x.  ``panel_widths``: the C for which the panel kernel has a form of this projection."""
+        assert ln is None or bias is None
+        if ln is None:
+            (w, self.alpha), = parts
+            assert self.alpha == 1.0
+            self.w, self.b, self.s = lin_w(w, device), vec(bias, device), None
+            self.alpha_cols = 0
+        else:
+            folded = [ln_fold(w, *ln, None, device, scale=a) for w, a in parts]
+            self.w = torch.cat([f[0] for f in folded], 0).contiguous()
+            self.s = torch.cat([f[1] for f in folded]).contiguous()
+            self.b = torch.cat([f[2] for f in folded]).contiguous()          # t of ln_fold, alpha_i already in it
+            self.alpha = parts[0][1]
+            self.alpha_cols = folded[0][0].shape[0] if len(parts) > 1 else 0      # (alpha on the leading columns only)
+        self.N, C = self.w.shape
+        # rows of the WHOLE call from which the panel form runs (None: igemm only).  Small calls: a persistent panel kernel with fewer
+        # panels than CUs loses to the igemm's small tiles; C = 320 takes the panel at every size
+        self.panel_from = None
+        if C in panel_widths and hip.LINEAR320 and (C == 320 or hip.LINEAR640):
+            self.panel_from = 0 if C == 320 else (hip.PANEL_MIN_ROWS_QKV640 if len(parts) == 3 else hip.PANEL_MIN_ROWS_LIN640)
+            # panel operands: bias / LayerNorm fold in the fold k-step (wx), one alpha per block of 320 output columns.  The kernel
+            # multiplies the whole bracket by alpha * rstd, so the fold columns carry t / alpha
+            if ln is None:
+                self.wx, self.al = ffn_fold_columns(torch.zeros(self.N, dtype=torch.float32, device=device), self.b), None
+            else:
+                self.wx = ffn_fold_columns(self.s, torch.cat([f[2] / a for f, (_, a) in zip(folded, parts)]))
+                self.al = torch.tensor([a for w, a in parts for _ in range(w.shape[0] // 320)], dtype=torch.float32, device=device)
+        # C = 320 fused Q / K / V: the panel kernel can store the V third TRANSPOSED per sample (``vt`` / ``hw`` of the call)
+        self.vt_form = C == 320 and len(parts) == 3 and self.panel_from is not None and hip.QKV_VT
+
+    def _panel(self, rows: int) -> bool:
+        # (hip.FORCE_TILE - "run what the big batch runs" - takes the panel kernels at any size)
+        return self.panel_from is not None and (rows >= self.panel_from or bool(hip.FORCE_TILE))
+
+    def __call__(self, x, rows, ln_stats=None, residual=None, want_stats=False, out=None, stats_out=None, vt=None, hw=0, gn_hw=0):
+        """``rows``: the rows of the whole call, which choose the kernel - so that the CFG-shared prefix (x holds half of them) takes
+        the kernels the unshared forward takes.  ``ln_stats``: the producer's row statistics (a projection built with ``ln``)."""
+        if self._panel(rows):
+            return hip.linear320(x, self.w, self.wx, ln_stats=ln_stats, alpha=self.al, residual=residual, out=out,
+                                 want_stats=want_stats, stats_out=stats_out, vt=vt, hw=hw)
+        assert vt is None and stats_out is None
+        return hip.linear(x, self.w, self.b, residual=residual, out=out, alpha=self.alpha, alpha_cols=self.alpha_cols,
+                          ln=(ln_stats, self.s) if self.s is not None else None, want_stats=want_stats, gn_hw=gn_hw)
+
+    def shared(self, x, rows, residual, want_stats=False, out=None, gn_hw=0):
+        """The two CFG halves of x [rows, C] against ONE residual [rows / 2, N] - the stream they still share - read with batch
+        stride 0; writes both halves."""
+        assert self.s is None
+        Mb, (N, K) = rows // 2, self.w.shape
+        if out is None:
+            out = torch.empty((rows, N), dtype=BF16, device=x.device)
+        if self._panel(rows):       # (the same kernel, row for row, as the unshared forward runs: the shared prefix stays EXACT)
+            st = torch.empty((rows, 2), dtype=torch.float32, device=x.device) if want_stats else None
+            for half in (slice(0, Mb), slice(Mb, 2 * Mb)):
+                self(x[half], rows, residual=residual, out=out[half], want_stats=want_stats, stats_out=st[half] if want_stats else None)
+        else:
+            st = hip.gemm(x, self.w, out, M=Mb, N=N, K=K, ldx=K, ldw=K, ldc=N, bias=self.b, residual=residual, ldr=N, batch=2,
+                          sX=Mb * K, sW=0, sC=Mb * N, sR=0, want_stats=want_stats, gn_hw=gn_hw)
+        return (out, st) if want_stats else out
+
+
+class _FeedForward:
+    """x + ff.net.2(GEGLU(ff.net.0(norm3(x)))), norm3 folded into ff.net.0: two igemm launches, or - C = 320 - ONE launch
+    (sdv_ffn_geglu_bf16) in which the hidden activations never leave the registers and the LayerNorm fold's per-column terms ride in
+    the matrix product (w1x)."""
+
+    def __init__(self, sd: StateDict, p: str, name: str, ln, device):
+        self.name = name
+        self.w1, self.s1, self.b1 = ln_fold(geglu_interleave(sd[p + ".net.0.proj.weight"]), *ln,
+                                            geglu_interleave(sd[p + ".net.0.proj.bias"]), device)
+        self.w2, self.b2 = lin_w(sd[p + ".net.2.weight"], device), vec(sd[p + ".net.2.bias"], device)
+        self.fused = hip.FFN_FUSED and self.w2.shape[0] == 320
+        if self.fused:
+            self.w1x = ffn_fold_columns(self.s1, self.b1)
+            self.w2p = ffn_w2_permute(self.w2)
+
+    def __call__(self, h, rows, ln_stats):
+        """``rows``: the rows of the whole call (below hip.PANEL_MIN_ROWS_FFN the persistent fused kernel leaves most CUs idle)."""
+        if self.fused and (rows >= hip.PANEL_MIN_ROWS_FFN or bool(hip.FORCE_TILE)):
+            return hip.ffn_geglu(h, ln_stats, self.w1, self.w1x, self.w2p, self.b2)
+        g = hip.linear(h, self.w1, self.b1, epi=1, ln=(ln_stats, self.s1))   # [M, 4C]
+        _aux(self.name, "ff_hidden", g)
+        return hip.linear(g, self.w2, self.b2, residual=h)
+
+
 class _Transformer:
     """Transformer2DModel with one BasicTransformerBlock (self-attn, text cross-attn, GEGLU FF)."""
 
     def __init__(self, sd: StateDict, p: str, device, heads: int, groups: int):
         self.name = p
         self.gn_g, self.gn_b = vec(sd[p + ".norm.weight"], device), vec(sd[p + ".norm.bias"], device)
-        self.w_in, self.b_in = lin_w(sd[p + ".proj_in.weight"], device), vec(sd[p + ".proj_in.bias"], device)
-        self.w_out, self.b_out = lin_w(sd[p + ".proj_out.weight"], device), vec(sd[p + ".proj_out.bias"], device)
         b = p + ".transformer_blocks.0"
-        self.C = self.w_in.shape[0]
+        self.C = sd[p + ".proj_in.weight"].shape[0]
         self.heads = heads
         self.dh = self.C // heads
+        self.groups = groups
         qs = hip.q_prescale(self.dh)       # softmax scale * log2(e): the alpha of every Q projection (hip.attention, q_prescaled)
-        # The three LayerNorms are folded into the GEMMs they feed (weights.ln_fold / sdv_hip.h ln_side): the GEMM that
-        # PRODUCES the normalised tensor also emits its row statistics, the consumers read the un-normalised tensor.
         ln1, ln2, ln3 = ((sd[f"{b}.norm{i}.weight"], sd[f"{b}.norm{i}.bias"]) for i in (1, 2, 3))
+        free = (320, 640)                  # panel forms: every projection at C = 320, the residual-free ones at C = 640 too
+        self.proj_in = _Proj([(sd[p + ".proj_in.weight"], 1.0)], sd[p + ".proj_in.bias"], device, panel_widths=free)
         # attn1.to_q / to_k / to_v as ONE projection [3C, C] = [Wq' ; Wk' ; Wv'] (norm1 folded into all three): the attention
         # kernel reads Q, K and V straight out of its [tokens, 3C] output - V row-major, transposed in the kernel's LDS read
         # (sdv_attention_bf16 v_rowmajor) - so the self-attention is 2 launches.  Rounds 2-4 ran a separate TRANSPOSED V^T
         # projection (column-side LayerNorm fold) per block; DESIGN.md tells what went wrong with it.
-        wq, sq, tq = ln_fold(sd[f"{b}.attn1.to_q.weight"], *ln1, None, device, scale=qs)
-        wk, sk, tk = ln_fold(sd[f"{b}.attn1.to_k.weight"], *ln1, None, device)
-        wv, sv, tv = ln_fold(sd[f"{b}.attn1.to_v.weight"], *ln1, None, device)
-        self.wqkv1 = torch.cat([wq, wk, wv], 0).contiguous()
-        self.sqkv1, self.tqkv1 = torch.cat([sq, sk, sv]).contiguous(), torch.cat([tq, tk, tv]).contiguous()
-        self.wo1, self.bo1 = lin_w(sd[f"{b}.attn1.to_out.0.weight"], device), vec(sd[f"{b}.attn1.to_out.0.bias"], device)
-        self.wq2, self.sq2, self.tq2 = ln_fold(sd[f"{b}.attn2.to_q.weight"], *ln2, None, device, scale=qs)
+        self.qkv1 = _Proj([(sd[f"{b}.attn1.to_q.weight"], qs), (sd[f"{b}.attn1.to_k.weight"], 1.0), (sd[f"{b}.attn1.to_v.weight"], 1.0)],
+                          None, device, ln=ln1, panel_widths=free)
+        self.to_out1 = _Proj([(sd[f"{b}.attn1.to_out.0.weight"], 1.0)], sd[f"{b}.attn1.to_out.0.bias"], device, panel_widths=(320,))
+        self.q2 = _Proj([(sd[f"{b}.attn2.to_q.weight"], qs)], None, device, ln=ln2, panel_widths=free)
         self.wk2 = lin_w(sd[f"{b}.attn2.to_k.weight"], device)
         self.wv2 = lin_w(sd[f"{b}.attn2.to_v.weight"], device)
-        self.wo2, self.bo2 = lin_w(sd[f"{b}.attn2.to_out.0.weight"], device), vec(sd[f"{b}.attn2.to_out.0.bias"], device)
-        self.wff1, self.sff1, self.bff1 = ln_fold(geglu_interleave(sd[f"{b}.ff.net.0.proj.weight"]), *ln3,
-                                                  geglu_interleave(sd[f"{b}.ff.net.0.proj.bias"]), device)
-        self.wff2, self.bff2 = lin_w(sd[f"{b}.ff.net.2.weight"], device), vec(sd[f"{b}.ff.net.2.bias"], device)
-        # C = 320 (the 64 x 64 level): norm3 -> ff.net.0 -> GEGLU -> ff.net.2 -> + residual is ONE launch (sdv_ffn_geglu_bf16) - the
-        # hidden activations never leave the registers; the LayerNorm fold's per-column terms ride in the matrix product (w1x)
-        self.ffn_fused = hip.FFN_FUSED and self.C == 320
-        # C = 320: proj_in, the fused Q / K / V projection, attn1.to_out, attn2.to_q and attn2.to_out run on the panel kernel
-        # (sdv_linear320_bf16): bias / LayerNorm fold in the fold k-step (wx), the row statistics leave as (mean, rstd) directly
-        self.lin320 = hip.LINEAR320 and self.C == 320
-        # C = 640 (the 32 x 32 level): the residual-free three of them - proj_in, the fused Q / K / V projection, attn2.to_q - on the
-        # same kernel's 10-slab form (sdv_linear640_bf16); the two to_out projections keep their residual on the igemm
-        self.lin640 = hip.LINEAR320 and hip.LINEAR640 and self.C == 640
-        self.linp = self.lin320 or self.lin640
-        if self.linp:
-            z = torch.zeros(self.C, dtype=torch.float32, device=device)
-            nb320 = self.C // 320                        # alpha: one factor per block of 320 output columns
-            self.wx_in = ffn_fold_columns(z, self.b_in)
-            # (the fold columns carry t / alpha: the kernel multiplies the whole bracket by alpha * rstd)
-            self.wx_qkv = ffn_fold_columns(self.sqkv1, torch.cat([tq / qs, tk, tv]))
-            self.al_qkv = torch.tensor([qs] * nb320 + [1.0] * (2 * nb320), dtype=torch.float32, device=device)
-            self.wx_q2 = ffn_fold_columns(self.sq2, self.tq2 / qs)
-            self.al_q2 = torch.tensor([qs] * nb320, dtype=torch.float32, device=device)
-        if self.lin320:
-            self.wx_o1 = ffn_fold_columns(z, self.bo1)
-            self.wx_o2 = ffn_fold_columns(z, self.bo2)
-        if self.ffn_fused:
-            self.w1x = ffn_fold_columns(self.sff1, self.bff1)
-            self.w2p = ffn_w2_permute(self.wff2)
-        self.groups = groups
-        # A/B switch (tools/unet_ab.py): SDV_LN_FOLD=0 keeps the three LayerNorms as kernels of their own
-        self.fold = os.environ.get("SDV_LN_FOLD", "1") != "0"
-        if not self.fold:
-            self.ln_plain = [(vec(sd[f"{b}.norm{i}.weight"], device), vec(sd[f"{b}.norm{i}.bias"], device)) for i in (1, 2, 3)]
-            self.p_wqkv1 = lin_w(torch.cat([sd[f"{b}.attn1.to_q.weight"], sd[f"{b}.attn1.to_k.weight"],
-                                            sd[f"{b}.attn1.to_v.weight"]], 0), device)
-            self.p_wq2 = lin_w(sd[f"{b}.attn2.to_q.weight"], device)
-            self.p_wff1 = lin_w(geglu_interleave(sd[f"{b}.ff.net.0.proj.weight"]), device)
-            self.p_bff1 = vec(geglu_interleave(sd[f"{b}.ff.net.0.proj.bias"]), device)
+        self.to_out2 = _Proj([(sd[f"{b}.attn2.to_out.0.weight"], 1.0)], sd[f"{b}.attn2.to_out.0.bias"], device, panel_widths=(320,))
+        self.ff = _FeedForward(sd, b + ".ff", p, ln3, device)
+        # (always the igemm: its epilogue emits the GroupNorm statistics of the block's output)
+        self.proj_out = _Proj([(sd[p + ".proj_out.weight"], 1.0)], sd[p + ".proj_out.bias"], device)
         # per batch size: (K [N*Lc, C], V^T [N, C, ldv] zero padded, Lc) - persistent so captured graphs stay valid
         self.ctx: Dict[int, tuple] = {}            # the (K, V^T, Lc) the next forward of a given batch size uses
         self.ctx_by_len: Dict[tuple, tuple] = {}
@@ -267,140 +323,59 @@ class _Transformer:
         """x: [nimg*HW, C] tokens.  With ``shared_prefix`` x holds only nimg/2 samples whose two CFG copies
         (unconditional / conditional) are still identical: everything up to the cross-attention - GroupNorm, proj_in,
         the whole self-attention, the cross-attention query - is computed ONCE, and the batch doubles where the
-        text context first enters (returns nimg samples)."""
+        text context first enters (returns nimg samples).
+
+        The three LayerNorms live inside the projections they feed: each producer emits the (mean, rstd) of its rows (st1 .. st3)."""
         C, HW, heads, dh = self.C, H * W, self.heads, self.dh
         nb = nimg // 2 if shared_prefix else nimg          # samples in the context-free prefix
-        Mb, M = nb * HW, nimg * HW
+        Mb, M = nb * HW, nimg * HW                         # (every projection chooses its kernel by M, the rows of the WHOLE call)
         scale = dh ** -0.5
-        if not self.fold:
-            return self._call_unfolded(x, nimg, H, W, shared_prefix, out, ctx_of)
-        # small calls: a persistent panel kernel with fewer panels than CUs loses to the igemm's small tiles (hip.PANEL_MIN_ROWS_*); the
-        # choice is made on the rows of the WHOLE call so that the CFG-shared prefix takes the kernels the unshared forward takes
-        forced = bool(hip.FORCE_TILE)
-        ffn_fused = self.ffn_fused and (forced or M >= hip.PANEL_MIN_ROWS_FFN)
-        lin_in = self.lin320 or (self.lin640 and (forced or M >= hip.PANEL_MIN_ROWS_LIN640))          # proj_in, attn2.to_q
-        lin_qkv = self.lin320 or (self.lin640 and (forced or M >= hip.PANEL_MIN_ROWS_QKV640))
         h = hip.groupnorm(x, self.gn_g, self.gn_b, nimg=nb, HW=HW, groups=self.groups, eps=1e-6, silu=False)
-        if lin_in:
-            h, st1 = hip.linear320(h, self.w_in, self.wx_in, want_stats=True)
-        else:
-            h, st1 = hip.linear(h, self.w_in, self.b_in, want_stats=True)        # + (mean, rstd) of every token for norm1
+        h, st1 = self.proj_in(h, M, want_stats=True)
         _tap(self.name, "tf_in", x=x, out=h, nimg=nb, H=H, W=W)
         h_in = h
-        # --- self attention: LN1 lives inside the fused Q / K / V projection ---
-        qs = hip.q_prescale(dh)       # softmax scale * log2(e), applied by the Q projections before their single rounding
+        # --- self attention ---
         o = torch.empty((Mb, C), dtype=BF16, device=x.device)
-        if self.lin320 and HW % 128 == 0 and hip.QKV_VT:
+        if self.qkv1.vt_form and HW % 128 == 0:
             # [Q * qs | K] row-major + V TRANSPOSED per sample, straight out of the projection's epilogue: the attention kernel's
             # one-read-per-fragment form (4 % faster than the transposing LDS reads of the row-major V at dh 40)
             vt = torch.empty((nb, C, HW), dtype=BF16, device=x.device)
-            qk = hip.linear320(h, self.wqkv1, self.wx_qkv, ln_stats=st1, alpha=self.al_qkv, vt=vt, hw=HW)
+            qk = self.qkv1(h, M, ln_stats=st1, vt=vt, hw=HW)
             hip.attention(qk, qk, vt, o, B=nb, H=heads, Lq=HW, Lk=HW, dh=dh, ldq=2 * C, ldk=2 * C, ldv=HW, ldo=C, scale=scale, k_off=C,
                           q_prescaled=True)
         else:
-            if lin_qkv:
-                qkv = hip.linear320(h, self.wqkv1, self.wx_qkv, ln_stats=st1, alpha=self.al_qkv)      # [Mb, 3C] = [Q * qs | K | V]
-            else:
-                qkv = hip.linear(h, self.wqkv1, self.tqkv1, alpha=qs, alpha_cols=C, ln=(st1, self.sqkv1))
+            qkv = self.qkv1(h, M, ln_stats=st1)              # [Mb, 3C] = [Q * qs | K | V]
             hip.attention(qkv, qkv, qkv, o, B=nb, H=heads, Lq=HW, Lk=HW, dh=dh, ldq=3 * C, ldk=3 * C, ldv=3 * C, ldo=C,
                           scale=scale, k_off=C, v_off=2 * C, q_prescaled=True, v_rowmajor=True)
-        if self.lin320:
-            h, st2 = hip.linear320(o, self.wo1, self.wx_o1, residual=h, want_stats=True)
-        else:
-            h, st2 = hip.linear(o, self.wo1, self.bo1, residual=h, want_stats=True)
+        h, st2 = self.to_out1(o, M, residual=h, want_stats=True)
         _tap(self.name, "tf_attn1", x=h_in, out=h, nimg=nb, H=H, W=W)
         h_in = h
-        # --- cross attention on the text context (LN2 inside the Q projection) ---
-        if lin_in:
-            q = hip.linear320(h, self.wq2, self.wx_q2, ln_stats=st2, alpha=self.al_q2)
-        else:
-            q = hip.linear(h, self.wq2, self.tq2, alpha=qs, ln=(st2, self.sq2))
+        # --- cross attention on the text context ---
+        q = self.q2(h, M, ln_stats=st2)
         o2 = torch.empty((M, C), dtype=BF16, device=x.device)
         ctx_k, ctx_vt, Lc = self._context(nimg, ctx_of)
         if not shared_prefix:
             hip.attention(q, ctx_k, ctx_vt, o2, B=nimg, H=heads, Lq=HW, Lk=Lc, dh=dh, ldq=C, ldk=C, ldv=ctx_vt.shape[2],
                           ldo=C, scale=scale, q_prescaled=True)
-            if self.lin320:
-                h, st3 = hip.linear320(o2, self.wo2, self.wx_o2, residual=h, want_stats=True)
-            else:
-                h, st3 = hip.linear(o2, self.wo2, self.bo2, residual=h, want_stats=True)
+            h, st3 = self.to_out2(o2, M, residual=h, want_stats=True)
         else:
             # same queries against the unconditional and the conditional context; the residual stream h is still
             # shared, so the output projection reads it with batch stride 0 and writes both halves
             for half in range(2):
                 hip.attention(q, ctx_k[half * nb * Lc:], ctx_vt[half * nb:], o2[half * Mb:], B=nb, H=heads, Lq=HW, Lk=Lc,
                               dh=dh, ldq=C, ldk=C, ldv=ctx_vt.shape[2], ldo=C, scale=scale, q_prescaled=True)
-            h2 = torch.empty((M, C), dtype=BF16, device=x.device)
-            if self.lin320:       # (the same kernel, row for row, as the unshared forward runs: the shared prefix stays EXACT)
-                st3 = torch.empty((M, 2), dtype=torch.float32, device=x.device)
-                for half in range(2):
-                    hip.linear320(o2[half * Mb:(half + 1) * Mb], self.wo2, self.wx_o2, residual=h, out=h2[half * Mb:(half + 1) * Mb],
-                                  want_stats=True, stats_out=st3[half * Mb:(half + 1) * Mb])
-            else:
-                st3 = hip.gemm(o2, self.wo2, h2, M=Mb, N=C, K=C, ldx=C, ldw=C, ldc=C, bias=self.bo2, residual=h, ldr=C, batch=2,
-                               sX=Mb * C, sW=0, sC=Mb * C, sR=0, want_stats=True)
-            h = h2
+            h, st3 = self.to_out2.shared(o2, M, residual=h, want_stats=True)
         _tap(self.name, "tf_attn2", x=h_in, out=h, nimg=nb, H=H, W=W, shared_prefix=shared_prefix)
         _aux(self.name, "st3", st3)
         h_in = h
-        # --- GEGLU feed-forward (LN3 inside ff.net.0) ---
-        if ffn_fused:
-            h = hip.ffn_geglu(h, st3, self.wff1, self.w1x, self.w2p, self.bff2)
-        else:
-            g = hip.linear(h, self.wff1, self.bff1, epi=1, ln=(st3, self.sff1))   # [M, 4C]
-            _aux(self.name, "ff_hidden", g)
-            h = hip.linear(g, self.wff2, self.bff2, residual=h)
+        # --- GEGLU feed-forward ---
+        h = self.ff(h, M, st3)
         _tap(self.name, "tf_ff", x=h_in, out=h, nimg=nimg, H=H, W=W)
         if not shared_prefix:
-            out = hip.linear(h, self.w_out, self.b_out, residual=x, out=out, gn_hw=HW)
+            out = self.proj_out(h, M, residual=x, out=out, gn_hw=HW)
         else:
-            if out is None:
-                out = torch.empty((M, C), dtype=BF16, device=x.device)       # residual x is the shared (nb-sample) input
-            hip.gemm(h, self.w_out, out, M=Mb, N=C, K=C, ldx=C, ldw=C, ldc=C, bias=self.b_out, residual=x, ldr=C, batch=2,
-                     sX=Mb * C, sW=0, sC=Mb * C, sR=0, gn_hw=HW)
+            out = self.proj_out.shared(h, M, residual=x, out=out, gn_hw=HW)       # residual x is the shared (nb-sample) input
         _tap(self.name, "tf_out", x=h, x2=x, out=out, nimg=nimg, H=H, W=W, shared_prefix=shared_prefix)
-        return out
-
-
-    def _call_unfolded(self, x, nimg, H, W, shared_prefix, out=None, ctx_of=None):
-        """The same block with the three LayerNorms as stand-alone kernels (A/B reference for the fold, SDV_LN_FOLD=0)."""
-        C, HW, heads, dh = self.C, H * W, self.heads, self.dh
-        nb = nimg // 2 if shared_prefix else nimg
-        Mb, M = nb * HW, nimg * HW
-        scale, qs = dh ** -0.5, hip.q_prescale(dh)
-        h = hip.groupnorm(x, self.gn_g, self.gn_b, nimg=nb, HW=HW, groups=self.groups, eps=1e-6, silu=False)
-        h = hip.linear(h, self.w_in, self.b_in)
-        n1 = hip.layernorm(h, *self.ln_plain[0])
-        qkv = hip.linear(n1, self.p_wqkv1, alpha=qs, alpha_cols=C)
-        o = torch.empty((Mb, C), dtype=BF16, device=x.device)
-        hip.attention(qkv, qkv, qkv, o, B=nb, H=heads, Lq=HW, Lk=HW, dh=dh, ldq=3 * C, ldk=3 * C, ldv=3 * C, ldo=C,
-                      scale=scale, k_off=C, v_off=2 * C, q_prescaled=True, v_rowmajor=True)
-        h = hip.linear(o, self.wo1, self.bo1, residual=h)
-        n2 = hip.layernorm(h, *self.ln_plain[1])
-        q = hip.linear(n2, self.p_wq2, alpha=qs)
-        o2 = torch.empty((M, C), dtype=BF16, device=x.device)
-        ctx_k, ctx_vt, Lc = self._context(nimg, ctx_of)
-        if not shared_prefix:
-            hip.attention(q, ctx_k, ctx_vt, o2, B=nimg, H=heads, Lq=HW, Lk=Lc, dh=dh, ldq=C, ldk=C, ldv=ctx_vt.shape[2],
-                          ldo=C, scale=scale, q_prescaled=True)
-            h = hip.linear(o2, self.wo2, self.bo2, residual=h)
-        else:
-            for half in range(2):
-                hip.attention(q, ctx_k[half * nb * Lc:], ctx_vt[half * nb:], o2[half * Mb:], B=nb, H=heads, Lq=HW, Lk=Lc,
-                              dh=dh, ldq=C, ldk=C, ldv=ctx_vt.shape[2], ldo=C, scale=scale, q_prescaled=True)
-            h2 = torch.empty((M, C), dtype=BF16, device=x.device)
-            hip.gemm(o2, self.wo2, h2, M=Mb, N=C, K=C, ldx=C, ldw=C, ldc=C, bias=self.bo2, residual=h, ldr=C, batch=2,
-                     sX=Mb * C, sW=0, sC=Mb * C, sR=0)
-            h = h2
-        n3 = hip.layernorm(h, *self.ln_plain[2])
-        g = hip.linear(n3, self.p_wff1, self.p_bff1, epi=1)
-        h = hip.linear(g, self.wff2, self.bff2, residual=h)
-        if not shared_prefix:
-            return hip.linear(h, self.w_out, self.b_out, residual=x, out=out)
-        if out is None:
-            out = torch.empty((M, C), dtype=BF16, device=x.device)
-        hip.gemm(h, self.w_out, out, M=Mb, N=C, K=C, ldx=C, ldw=C, ldc=C, bias=self.b_out, residual=x, ldr=C, batch=2,
-                 sX=Mb * C, sW=0, sC=Mb * C, sR=0)
         return out
 
 

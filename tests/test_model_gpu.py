@@ -547,6 +547,19 @@ def test_cfg_shared_prefix_is_exact(hip, dev):
         assert float((a[:2] - a[2:]).abs().max()) > 1e-3      # the two halves really differ (different text context)
 
 
+@pytest.mark.parametrize("arch", ["tiny", "sd14"])
+def test_unet_launch_trace_on_the_device(hip, dev, arch):
+    """What the GPU is handed is what tests/test_launch_trace_cpu.py pins on the meta device: the same recorder around a real
+    forward - real pointers in ``hip.gn_epilogue_ok``, live version counters - gives the golden trace of the same case."""
+    import launch_trace as lt
+    size = (4, 16, True, 0)
+    want = json.loads(lt.GOLDEN_FILE.read_text())["unet/" + lt.engine_case_name(arch, size)]
+    trace = lt.trace_engine(lt.build_engine(arch, dev), *size)
+    torch.cuda.synchronize()
+    diff = lt.first_difference(trace, want)
+    assert diff is None, diff
+
+
 @pytest.mark.parametrize("fp8", [False, True])
 def test_cache_blocked_forward(hip, dev, fp8, monkeypatch):
     """UNetEngine._segment walks a ResBlock (+ transformer) over the batch in cache-sized chunks of images.  Every op of those

@@ -2,7 +2,7 @@
 """Which block of the UNet changes its output when ANOTHER process keeps the same GPU busy?
 (tests/test_model_gpu.py::test_bench_launches_its_own_ranks: two ranks on one GPU - a frame generated while the other rank was
 running differed, by a few uint8 steps and differently every time, from the same frame generated alone; one rank alone is
-bit-reproducible; SDV_LN_FOLD=0 makes the difference go away.)
+bit-reproducible; SDV_LN_FOLD=0 - a switch that existed up to the commit that introduced engine._Proj - made the difference go away.)
 Foreground: the tiny UNet's eager forward with engine.TAP recording every block / sub-block output - once alone (baseline), then
 RUNS times while a child process runs the same forward in a loop; per tap name the number of runs whose output differs from
 the baseline, in forward order (the first name with a non-zero count is where it starts).
