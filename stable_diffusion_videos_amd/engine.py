@@ -5,6 +5,9 @@
 ``VAEDecoderEngine.decode`` replaces ``self.vae.decode(latents).sample`` + the image epilogue
                             (stable_diffusion_pipeline.py:432-438, numpy_to_pil :450)
 
+Both are built from the same few objects: ``_Res`` (one body for the bf16 and the fp8 ResBlock), ``_Transformer``, ``_ConvIn``,
+``_Down`` / ``_Up``, grouped per resolution into ``_Level``; tests/launch_trace.py pins what each of them launches.
+
 Everything is NHWC / token-major bf16 in HBM ([N*H*W, C] row-major), so the UNet's conv <-> transformer
 boundaries need no permutes.  Each method only enqueues HIP kernels - through the wrappers of ``hip``, each of which
 dispatches one ``torch.ops.sdv.k_*`` custom op onto the C ABI of libsdv_hip.so - on the current stream: a whole denoise
@@ -19,7 +22,7 @@ What is hoisted out of the 50-step loop (the reference recomputes all of it ever
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -104,61 +107,102 @@ class _Res:
         # activation scales are calibrated on the first forward (2 x amax / 448: e4m3 is floating point, head-room is free).
         self.fp8 = fp8
         if fp8:
-            self.w1_8, self.sw1 = _quant_w(self.w1)
-            self.w2_8, self.sw2 = _quant_w(self.w2)
-            self.sx1: Optional[float] = None
-            self.sx2: Optional[float] = None
+            (w1_8, sw1), (w2_8, sw2) = _quant_w(self.w1), _quant_w(self.w2)
+            self.w8, self.sw = (w1_8, w2_8), (sw1, sw2)
+            self.sx: List[Optional[float]] = [None, None]     # e4m3 scales of the activations conv1 / conv2 read
             self.calibrating = False           # UNetEngine.fp8_calibration(): widen the scales on every forward (eager only)
 
     def prepare_timesteps(self, emb: torch.Tensor):
         self.bias_table = hip.linear_small(emb, self.wt, self.bt, add=self.c1_bias, silu_in=True)
 
-    def _call_fp8(self, x, x2, nimg, H, W, step_ptr, circular, out=None):
-        HW = H * W
-        gn = dict(nimg=nimg, HW=HW, groups=self.groups, eps=self.eps, silu=True)
+    def _gn_silu(self, i: int, x, x2, gamma, beta, gn):
+        """GroupNorm + SiLU of x (++ x2) in the operand format of the conv behind it, conv1 (i = 0) or conv2 (1) -> (the
+        activation, that conv's alpha)."""
+        if not self.fp8:
+            return hip.groupnorm(x, gamma, beta, x2=x2, **gn), 1.0
         # Activation scales: set by an explicit calibration run (UNetEngine.fp8_calibration - the pipeline runs a fixed pilot
         # denoise BEFORE the graph warm-up, so the scales never come from a zero-filled capture buffer and are the same on every
         # rank / resume); a bare engine (tests, tools) calibrates lazily on its first eager forward.
-        if self.sx1 is None or self.calibrating:
-            self.sx1 = _act_scale(hip.groupnorm(x, self.g1, self.b1, x2=x2, **gn), self.sx1)
-        h8 = hip.groupnorm(x, self.g1, self.b1, x2=x2, fp8_scale=self.sx1, **gn)
-        if self.wt is not None:
-            h = hip.conv3x3(h8, self.w1_8, self.bias_table, nimg=nimg, H=H, W=W, circular=circular, step_ptr=step_ptr,
-                            bias_step_stride=self.cout, alpha=self.sx1 * self.sw1)
-        else:
-            h = hip.conv3x3(h8, self.w1_8, self.c1_bias, nimg=nimg, H=H, W=W, circular=circular, alpha=self.sx1 * self.sw1)
-        if self.sx2 is None or self.calibrating:
-            self.sx2 = _act_scale(hip.groupnorm(h, self.g2, self.b2, **gn), self.sx2)
-        h8 = hip.groupnorm(h, self.g2, self.b2, fp8_scale=self.sx2, **gn)
-        sc = hip.linear(x, self.ws, self.bs, x2=x2) if self.ws is not None else x
-        return hip.conv3x3(h8, self.w2_8, self.c2_bias, nimg=nimg, H=H, W=W, residual=sc, circular=circular,
-                           alpha=self.sx2 * self.sw2, out=out)
+        if self.sx[i] is None or self.calibrating:
+            self.sx[i] = _act_scale(hip.groupnorm(x, gamma, beta, x2=x2, **gn), self.sx[i])
+        return hip.groupnorm(x, gamma, beta, x2=x2, fp8_scale=self.sx[i], **gn), self.sx[i] * self.sw[i]
 
     def __call__(self, x, x2, nimg, H, W, step_ptr, circular, out=None):
         """``out``: where the block's result goes (a row range of a larger tensor when the caller walks the batch in
         cache-sized chunks of images, UNetEngine._segment)."""
-        call = self._call_fp8 if self.fp8 else self._call_bf16
-        out = call(x, x2, nimg, H, W, step_ptr, circular, out=out)
+        gn = dict(nimg=nimg, HW=H * W, groups=self.groups, eps=self.eps, silu=True)
+        # (gn=True: the conv's epilogue also emits the per-channel statistics of what it stores, so norm2 - and, for conv2 below, the
+        #  next block's GroupNorm - runs no statistics pass of its own; hip.groupnorm picks them up from the tensor.  An fp8 conv has
+        #  no such epilogue: hip.gn_epilogue_ok refuses it)
+        conv = dict(nimg=nimg, H=H, W=W, circular=circular, gn=True)
+        w1, w2 = self.w8 if self.fp8 else (self.w1, self.w2)
+        h, alpha = self._gn_silu(0, x, x2, self.g1, self.b1, gn)
+        if self.wt is not None:
+            h = hip.conv3x3(h, w1, self.bias_table, step_ptr=step_ptr, bias_step_stride=self.cout, alpha=alpha, **conv)
+        else:
+            h = hip.conv3x3(h, w1, self.c1_bias, alpha=alpha, **conv)
+        h, alpha = self._gn_silu(1, h, None, self.g2, self.b2, gn)
+        assert self.ws is not None or x2 is None
+        sc = hip.linear(x, self.ws, self.bs, x2=x2) if self.ws is not None else x
+        out = hip.conv3x3(h, w2, self.c2_bias, residual=sc, alpha=alpha, out=out, **conv)
         _tap(self.name, "resnet", x=x, x2=x2, out=out, nimg=nimg, H=H, W=W)
         return out
 
-    def _call_bf16(self, x, x2, nimg, H, W, step_ptr, circular, out=None):
-        HW = H * W
-        h = hip.groupnorm(x, self.g1, self.b1, nimg=nimg, HW=HW, groups=self.groups, eps=self.eps, silu=True, x2=x2)
-        if self.wt is not None:
-            h = hip.conv3x3(h, self.w1, self.bias_table, nimg=nimg, H=H, W=W, circular=circular, step_ptr=step_ptr,
-                            bias_step_stride=self.cout, gn=True)
+
+class _ConvIn:
+    """conv_in of the UNet / the VAE decoder: from 4 channels on the matrix cores (im2col to one 64-wide K tile, whose epilogue emits
+    the GroupNorm statistics), from any other small count on the direct kernel."""
+
+    def __init__(self, sd: StateDict, p: str, device):
+        self.name = p
+        w = sd[p + ".weight"]
+        self.c4 = w.shape[1] == 4
+        self.w = conv_w_c4(w.cpu(), device) if self.c4 else conv_w(w, device)
+        self.b = vec(sd[p + ".bias"], device)
+
+    def __call__(self, x, nimg, H, W, circular):
+        if self.c4:
+            out = hip.conv3x3_c4(x, self.w, self.b, nimg=nimg, H=H, W=W, circular=circular, gn=True)
         else:
-            h = hip.conv3x3(h, self.w1, self.c1_bias, nimg=nimg, H=H, W=W, circular=circular, gn=True)
-        # (gn=True: the conv's epilogue also emits the per-channel statistics of what it stores, so norm2 - and, for conv2 below, the
-        #  next block's GroupNorm - runs no statistics pass of its own; hip.groupnorm picks them up from the tensor)
-        h = hip.groupnorm(h, self.g2, self.b2, nimg=nimg, HW=HW, groups=self.groups, eps=self.eps, silu=True)
-        if self.ws is not None:
-            sc = hip.linear(x, self.ws, self.bs, x2=x2)
-        else:
-            assert x2 is None
-            sc = x
-        return hip.conv3x3(h, self.w2, self.c2_bias, nimg=nimg, H=H, W=W, residual=sc, circular=circular, out=out, gn=True)
+            out = hip.conv3x3_cin_small(x, self.w, self.b, nimg=nimg, H=H, W=W, circular=circular)
+        _tap(self.name, "conv", x=x, out=out, nimg=nimg, H=H, W=W)
+        return out
+
+
+class _Down:
+    """Downsample2D: conv3x3 stride 2.  Returns the rows and their new height and width."""
+
+    def __init__(self, sd: StateDict, p: str, device):
+        self.name = p
+        self.w, self.b = conv_w(sd[p + ".conv.weight"], device), vec(sd[p + ".conv.bias"], device)
+
+    def __call__(self, x, nimg, H, W, circular):
+        out = hip.conv3x3(x, self.w, self.b, nimg=nimg, H=H, W=W, mode=2, circular=circular, gn=True)
+        _tap(self.name, "down", x=x, out=out, nimg=nimg, H=H, W=W)
+        return out, (H + 1) // 2, (W + 1) // 2
+
+
+class _Up:
+    """Upsample2D (nearest 2x + conv3x3) in phase form (weights.upconv_phase_w).  Returns the rows and their new height and width."""
+
+    def __init__(self, sd: StateDict, p: str, device):
+        self.name = p
+        self.w, self.b = upconv_phase_w(sd[p + ".conv.weight"], device), vec(sd[p + ".conv.bias"], device)
+
+    def __call__(self, x, nimg, H, W, circular):
+        out = hip.upconv3x3_phase(x, self.w, self.b, nimg=nimg, H=H, W=W, circular=circular, gn=True)
+        _tap(self.name, "up", x=x, out=out, nimg=nimg, H=H, W=W)
+        return out, 2 * H, 2 * W
+
+
+class _Level(NamedTuple):
+    """One resolution level of a down or an up path."""
+    res: List[_Res]
+    attn: list                  # the _Transformer behind each ResBlock, or empty
+    resample: Optional[object]  # the _Down / _Up that leaves the level; None at the last one
+
+    def pairs(self):
+        return zip(self.res, self.attn or [None] * len(self.res))
 
 
 class _Proj:
@@ -392,9 +436,7 @@ class UNetEngine:
         ch = cfg.block_out_channels
         g, eps = cfg.norm_num_groups, cfg.norm_eps
         dev = self.device
-        self.conv_in_c4 = cfg.in_channels == 4
-        self.conv_in_w = conv_w_c4(sd["conv_in.weight"].cpu(), dev) if self.conv_in_c4 else conv_w(sd["conv_in.weight"], dev)
-        self.conv_in_b = vec(sd["conv_in.bias"], dev)
+        self.conv_in = _ConvIn(sd, "conv_in", dev)
         self.t_w1, self.t_b1 = lin_w(sd["time_embedding.linear_1.weight"], dev), vec(sd["time_embedding.linear_1.bias"], dev)
         self.t_w2, self.t_b2 = lin_w(sd["time_embedding.linear_2.weight"], dev), vec(sd["time_embedding.linear_2.bias"], dev)
         self.res: List[_Res] = []
@@ -410,28 +452,23 @@ class UNetEngine:
             self.tfm.append(t)
             return t
 
-        self.down = []
+        last = len(ch) - 1
+        self.down: List[_Level] = []
         for i, typ in enumerate(cfg.down_block_types):
-            blk = {"res": [], "attn": [], "down": None}
+            blk = _Level([], [], _Down(sd, f"down_blocks.{i}.downsamplers.0", dev) if i != last else None)
             for j in range(cfg.layers_per_block):
-                blk["res"].append(res(f"down_blocks.{i}.resnets.{j}"))
+                blk.res.append(res(f"down_blocks.{i}.resnets.{j}"))
                 if typ.startswith("CrossAttn"):
-                    blk["attn"].append(tfm(f"down_blocks.{i}.attentions.{j}", i))
-            if i != len(ch) - 1:
-                blk["down"] = (conv_w(sd[f"down_blocks.{i}.downsamplers.0.conv.weight"], dev),
-                               vec(sd[f"down_blocks.{i}.downsamplers.0.conv.bias"], dev))
+                    blk.attn.append(tfm(f"down_blocks.{i}.attentions.{j}", i))
             self.down.append(blk)
-        self.mid = (res("mid_block.resnets.0"), tfm("mid_block.attentions.0", len(ch) - 1), res("mid_block.resnets.1"))
-        self.up = []
+        self.mid = (res("mid_block.resnets.0"), tfm("mid_block.attentions.0", last), res("mid_block.resnets.1"))
+        self.up: List[_Level] = []
         for i, typ in enumerate(cfg.up_block_types):
-            blk = {"res": [], "attn": [], "up": None}
+            blk = _Level([], [], _Up(sd, f"up_blocks.{i}.upsamplers.0", dev) if i != last else None)
             for j in range(cfg.layers_per_block + 1):
-                blk["res"].append(res(f"up_blocks.{i}.resnets.{j}"))
+                blk.res.append(res(f"up_blocks.{i}.resnets.{j}"))
                 if typ.startswith("CrossAttn"):
-                    blk["attn"].append(tfm(f"up_blocks.{i}.attentions.{j}", len(ch) - 1 - i))
-            if i != len(ch) - 1:
-                blk["up"] = (upconv_phase_w(sd[f"up_blocks.{i}.upsamplers.0.conv.weight"], dev),
-                             vec(sd[f"up_blocks.{i}.upsamplers.0.conv.bias"], dev))
+                    blk.attn.append(tfm(f"up_blocks.{i}.attentions.{j}", last - i))
             self.up.append(blk)
         self.out_g, self.out_b = vec(sd["conv_norm_out.weight"], dev), vec(sd["conv_norm_out.bias"], dev)
         self.conv_out_w = conv_w(sd["conv_out.weight"], dev)
@@ -452,15 +489,15 @@ class UNetEngine:
             if ok:
                 self.fp8_calibrated = True
             elif restore is not None:
-                for r, (a, b) in zip([r for r in self.res if r.fp8], restore):
-                    r.sx1, r.sx2 = a, b
+                for r, scales in zip([r for r in self.res if r.fp8], restore):
+                    r.sx = list(scales)
 
     def fp8_scales(self):
-        return [(r.sx1, r.sx2) for r in self.res if r.fp8]
+        return [tuple(r.sx) for r in self.res if r.fp8]
 
     def set_fp8_scales(self, scales):
         for r, (a, b) in zip([r for r in self.res if r.fp8], scales):
-            r.sx1, r.sx2 = float(a), float(b)
+            r.sx = [float(a), float(b)]
         self.fp8_calibrated = True
 
     # -- per-walk preparation ----------------------------------------------------------------
@@ -555,13 +592,9 @@ class UNetEngine:
         cross-attention the two copies compute identical values, so conv_in, the first ResBlock and the first
         transformer's self-attention run on nimg/2 samples only."""
         circ = self.tiled
-        shared = bool(cfg_shared) and nimg % 2 == 0 and bool(self.down[0]["attn"])
+        shared = bool(cfg_shared) and nimg % 2 == 0 and bool(self.down[0].attn)
         nb = nimg // 2 if shared else nimg
-        if self.conv_in_c4:
-            h = hip.conv3x3_c4(x[: nb * H * W], self.conv_in_w, self.conv_in_b, nimg=nb, H=H, W=W, circular=circ, gn=True)
-        else:
-            h = hip.conv3x3_cin_small(x[: nb * H * W], self.conv_in_w, self.conv_in_b, nimg=nb, H=H, W=W, circular=circ)
-        _tap("conv_in", "conv", x=x[: nb * H * W], out=h, nimg=nb, H=H, W=W)
+        h = self.conv_in(x[: nb * H * W], nb, H, W, circ)
         if shared:
             h0 = torch.empty((nimg * H * W, h.shape[1]), dtype=BF16, device=self.device)   # skip tensor for the up path
             h0[: nb * H * W].copy_(h)
@@ -572,30 +605,22 @@ class UNetEngine:
             skips = [h]
         hh, ww = H, W
         for bi, blk in enumerate(self.down):
-            for j, r in enumerate(blk["res"]):
+            for j, (r, t) in enumerate(blk.pairs()):
                 first = shared and bi == 0 and j == 0
-                h = self._segment(r, blk["attn"][j] if blk["attn"] else None, h, None, nimg, nb, hh, ww, step_ptr, circ, first)
+                h = self._segment(r, t, h, None, nimg, nb, hh, ww, step_ptr, circ, first)
                 skips.append(h)
-            if blk["down"] is not None:
-                wd, bd = blk["down"]
-                h_in = h
-                h = hip.conv3x3(h, wd, bd, nimg=nimg, H=hh, W=ww, mode=2, circular=circ, gn=True)
-                _tap(f"down_blocks.{bi}.downsamplers.0", "down", x=h_in, out=h, nimg=nimg, H=hh, W=ww)
-                hh, ww = (hh + 1) // 2, (ww + 1) // 2
+            if blk.resample is not None:
+                h, hh, ww = blk.resample(h, nimg, hh, ww, circ)
                 skips.append(h)
         r0, t0, r1 = self.mid
         h = r0(h, None, nimg, hh, ww, step_ptr, circ)
         h = t0(h, nimg, hh, ww)
         h = r1(h, None, nimg, hh, ww, step_ptr, circ)
-        for bi, blk in enumerate(self.up):
-            for j, r in enumerate(blk["res"]):
-                h = self._segment(r, blk["attn"][j] if blk["attn"] else None, h, skips.pop(), nimg, nb, hh, ww, step_ptr, circ)
-            if blk["up"] is not None:
-                wu, bu = blk["up"]
-                h_in = h
-                h = hip.upconv3x3_phase(h, wu, bu, nimg=nimg, H=hh, W=ww, circular=circ, gn=True)      # Upsample2D: nearest 2x + conv
-                _tap(f"up_blocks.{bi}.upsamplers.0", "up", x=h_in, out=h, nimg=nimg, H=hh, W=ww)
-                hh, ww = 2 * hh, 2 * ww
+        for blk in self.up:
+            for r, t in blk.pairs():
+                h = self._segment(r, t, h, skips.pop(), nimg, nb, hh, ww, step_ptr, circ)
+            if blk.resample is not None:
+                h, hh, ww = blk.resample(h, nimg, hh, ww, circ)
         h_in = h
         h = hip.groupnorm(h, self.out_g, self.out_b, nimg=nimg, HW=hh * ww, groups=self.groups, eps=self.eps, silu=True)
         eps = torch.empty((nimg, hh, ww, self.cfg.out_channels), dtype=F32, device=self.device)
@@ -620,10 +645,7 @@ class VAEDecoderEngine:
         lc = cfg.latent_channels
         self.pq_w = sd["post_quant_conv.weight"].reshape(lc, lc).contiguous().to(dev, F32)
         self.pq_b = vec(sd["post_quant_conv.bias"], dev)
-        self.conv_in_c4 = lc == 4
-        self.conv_in_w = (conv_w_c4(sd["decoder.conv_in.weight"].cpu(), dev) if self.conv_in_c4
-                          else conv_w(sd["decoder.conv_in.weight"], dev))
-        self.conv_in_b = vec(sd["decoder.conv_in.bias"], dev)
+        self.conv_in = _ConvIn(sd, "decoder.conv_in", dev)
         self.mid_res = [_Res(sd, f"decoder.mid_block.resnets.{i}", dev, g, 1e-6, False) for i in range(2)]
         a = "decoder.mid_block.attentions.0"
         self.a_g, self.a_b = vec(sd[a + ".group_norm.weight"], dev), vec(sd[a + ".group_norm.bias"], dev)
@@ -631,14 +653,9 @@ class VAEDecoderEngine:
         self.a_bqk = vec(torch.cat([sd[a + ".to_q.bias"], sd[a + ".to_k.bias"]], 0), dev)
         self.a_wv, self.a_bv = lin_w(sd[a + ".to_v.weight"], dev), vec(sd[a + ".to_v.bias"], dev)
         self.a_wo, self.a_bo = lin_w(sd[a + ".to_out.0.weight"], dev), vec(sd[a + ".to_out.0.bias"], dev)
-        self.up = []
-        for i in range(len(ch)):
-            blk = {"res": [_Res(sd, f"decoder.up_blocks.{i}.resnets.{j}", dev, g, 1e-6, False)
-                           for j in range(cfg.layers_per_block + 1)], "up": None}
-            if i != len(ch) - 1:
-                blk["up"] = (upconv_phase_w(sd[f"decoder.up_blocks.{i}.upsamplers.0.conv.weight"], dev),
-                             vec(sd[f"decoder.up_blocks.{i}.upsamplers.0.conv.bias"], dev))
-            self.up.append(blk)
+        self.up = [_Level([_Res(sd, f"decoder.up_blocks.{i}.resnets.{j}", dev, g, 1e-6, False) for j in range(cfg.layers_per_block + 1)],
+                          [], _Up(sd, f"decoder.up_blocks.{i}.upsamplers.0", dev) if i != len(ch) - 1 else None)
+                   for i in range(len(ch))]
         self.out_g, self.out_b = vec(sd["decoder.conv_norm_out.weight"], dev), vec(sd["decoder.conv_norm_out.bias"], dev)
         self.conv_out_w, self.conv_out_b = conv_w(sd["decoder.conv_out.weight"], dev), vec(sd["decoder.conv_out.bias"], dev)
         self.groups = g
@@ -646,11 +663,6 @@ class VAEDecoderEngine:
         self.score_chunk_bytes = 512 << 20      # mid-block attention: bytes of [HW, HW] bf16 scores materialised at a time
 
     def _attention(self, x, nimg, H, W):
-        out = self._attention_impl(x, nimg, H, W)
-        _tap("decoder.mid_block.attentions.0", "vae_attention", x=x, out=out, nimg=nimg, H=H, W=W)
-        return out
-
-    def _attention_impl(self, x, nimg, H, W):
         C, HW = x.shape[1], H * W
         n = hip.groupnorm(x, self.a_g, self.a_b, nimg=nimg, HW=HW, groups=self.groups, eps=1e-6, silu=False)
         qk = hip.linear(n, self.a_wqk, self.a_bqk)                                   # [M, 2C]
@@ -673,7 +685,9 @@ class VAEDecoderEngine:
             hip.softmax_rows_f32(s, pr, nb * HW, HW, HW, HW)
             hip.gemm(pr, vt, o, M=HW, N=C, K=HW, ldx=HW, ldw=HW, ldc=C, batch=nb, sX=HW * HW, sW=C * HW, sC=HW * C,
                      w_off=i0 * C * HW, out_off=i0 * HW * C)
-        return hip.linear(o, self.a_wo, self.a_bo, residual=x, gn_hw=HW)
+        out = hip.linear(o, self.a_wo, self.a_bo, residual=x, gn_hw=HW)
+        _tap("decoder.mid_block.attentions.0", "vae_attention", x=x, out=out, nimg=nimg, H=H, W=W)
+        return out
 
     def decode(self, latents: torch.Tensor, want_float: bool = False):
         """latents: fp32 NHWC [B, h, w, 4] (UNSCALED, as they leave the denoise loop).  Returns
@@ -683,23 +697,15 @@ class VAEDecoderEngine:
         z = torch.empty((B * h * w, lc), dtype=BF16, device=self.device)
         hip.latent_affine(latents.contiguous(), self.pq_w, self.pq_b, 1.0 / self.cfg.scaling_factor, z, B * h * w, lc)
         _tap("post_quant_conv", "post_quant", x=latents.reshape(B * h * w, lc), out=z, nimg=B, H=h, W=w)
-        if self.conv_in_c4:
-            x = hip.conv3x3_c4(z, self.conv_in_w, self.conv_in_b, nimg=B, H=h, W=w, circular=circ, gn=True)
-        else:
-            x = hip.conv3x3_cin_small(z, self.conv_in_w, self.conv_in_b, nimg=B, H=h, W=w, circular=circ)
-        _tap("decoder.conv_in", "conv", x=z, out=x, nimg=B, H=h, W=w)
+        x = self.conv_in(z, B, h, w, circ)
         x = self.mid_res[0](x, None, B, h, w, None, circ)
         x = self._attention(x, B, h, w)
         x = self.mid_res[1](x, None, B, h, w, None, circ)
-        for bi, blk in enumerate(self.up):
-            for r in blk["res"]:
+        for blk in self.up:
+            for r in blk.res:
                 x = r(x, None, B, h, w, None, circ)
-            if blk["up"] is not None:
-                wu, bu = blk["up"]
-                x_in = x
-                x = hip.upconv3x3_phase(x, wu, bu, nimg=B, H=h, W=w, circular=circ, gn=True)
-                _tap(f"decoder.up_blocks.{bi}.upsamplers.0", "up", x=x_in, out=x, nimg=B, H=h, W=w)
-                h, w = 2 * h, 2 * w
+            if blk.resample is not None:
+                x, h, w = blk.resample(x, B, h, w, circ)
         x_in = x
         x = hip.groupnorm(x, self.out_g, self.out_b, nimg=B, HW=h * w, groups=self.groups, eps=1e-6, silu=True)
         oc = self.cfg.out_channels

@@ -3,10 +3,10 @@
     safety_checker_input = self.feature_extractor(self.numpy_to_pil(image), return_tensors="pt")     :441
     image, has_nsfw_concept = self.safety_checker(images=image, clip_input=...pixel_values)          :442-447
 
-``CLIPVisionEngine`` is ``transformers.CLIPVisionModelWithProjection`` built the way ``text.CLIPTextEngine`` is - pre-LN blocks on
-``hip.linear`` / ``hip.layernorm`` / ``hip.attention`` (fused QKV projection with the softmax scale on Q, quick_gelu in the fc1
-epilogue, residual adds in the out-proj / fc2 epilogues); ``SafetyCheckerEngine`` puts the two kernels of csrc/sdv_vision.hip around
-it: ``hip.clip_preprocess_patches`` (CLIPImageProcessor + the patch convolution's im2col, uint8 frames in HBM -> GEMM operand) and
+``CLIPVisionEngine`` is ``transformers.CLIPVisionModelWithProjection`` on the encoder layer ``text.CLIPTextEngine`` runs too
+(``clip.EncoderLayer``), with one non-causal attention launch per image; ``SafetyCheckerEngine`` puts the two kernels of
+csrc/sdv_vision.hip around it:
+``hip.clip_preprocess_patches`` (CLIPImageProcessor + the patch convolution's im2col, uint8 frames in HBM -> GEMM operand) and
 ``hip.safety_screen`` (cosine head + black-out).  No CPU fallback: off the GPU the engines raise ``SdvHipError``.
 
 Token layout.  An image has T = (S/P)^2 + 1 tokens (257 for ViT-L/14 at 224), not a multiple of 32.  Activations are
@@ -34,7 +34,10 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .config import VisionConfig
+from . import hip
+from .clip import EncoderLayer, Engine
+from .config import VisionConfig, vision_from_json
+from .weights import SAFETY_HEAD_KEYS, lin_w, load_safety_checker, synthetic_safety_checker, vec, vision_shapes
 
 logger = logging.getLogger("stable_diffusion_videos_amd")
 
@@ -128,70 +131,37 @@ def _tower_key(sd, key):
     raise KeyError(key)
 
 
-class CLIPVisionEngine:
+class CLIPVisionEngine(Engine):
     """``CLIPVisionModelWithProjection(pixel_values).image_embeds`` on the HIP kernels, from the patch-embedding GEMM operand
     (``hip.clip_preprocess_patches``; column order (c, py, px), K padded to a multiple of 64)."""
 
     def __init__(self, cfg: VisionConfig, state_dict):
-        if cfg.hidden_size % cfg.num_attention_heads or cfg.hidden_size // cfg.num_attention_heads not in (40, 64, 80, 160):
-            raise ValueError("CLIPVisionEngine: head dim must be one of 40 / 64 / 80 / 160 (ViT-L/14 uses 64)")
-        if cfg.hidden_act not in ("quick_gelu", "gelu"):
-            raise ValueError(f"CLIPVisionEngine: unsupported hidden_act {cfg.hidden_act}")
+        super().__init__(cfg, state_dict)
         if cfg.image_size % cfg.patch_size or cfg.hidden_size % 8:
             raise ValueError("CLIPVisionEngine: image_size must be a multiple of patch_size and hidden_size of 8")
-        self.config = cfg
-        self.state_dict_ = state_dict
-        self.device = torch.device("cpu")
-        self._w = None
         self.T = cfg.num_tokens
         self.Tpad = (self.T + 31) // 32 * 32
 
-    def state_dict(self):
-        return self.state_dict_
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type == "cuda" and (self._w is None or device != self.device):
-            from . import hip
-            from .weights import lin_w, vec
-            hip.load()
-            c = self.config
-            sd = {k: _tower_key(self.state_dict_, k) for k in self._keys()}
-            D, K = c.hidden_size, 3 * c.patch_size ** 2
-            wp = torch.zeros((D, hip.patch_kpad(c.patch_size)), dtype=torch.float32)
-            wp[:, :K] = sd["embeddings.patch_embedding.weight"].float().reshape(D, K)
-            pos = sd["embeddings.position_embedding.weight"].float()
-            w = {"patch": lin_w(wp, device),
-                 # position embeddings of the patch tokens: the residual of the patch GEMM; class token row = class + position 0
-                 "pos": pos[1:].contiguous().to(device, torch.bfloat16),
-                 "cls": (sd["embeddings.class_embedding"].float() + pos[0]).to(device, torch.bfloat16),
-                 "pre": (vec(sd["pre_layrnorm.weight"], device), vec(sd["pre_layrnorm.bias"], device)),
-                 "post": (vec(sd["post_layernorm.weight"], device), vec(sd["post_layernorm.bias"], device)),
-                 "proj": lin_w(sd["visual_projection.weight"], device), "layers": []}
-            qs = hip.q_prescale(D // c.num_attention_heads)
-            for i in range(c.num_hidden_layers):
-                p = f"encoder.layers.{i}."
-                a = p + "self_attn."
-                w["layers"].append(dict(
-                    ln1=(vec(sd[p + "layer_norm1.weight"], device), vec(sd[p + "layer_norm1.bias"], device)),
-                    ln2=(vec(sd[p + "layer_norm2.weight"], device), vec(sd[p + "layer_norm2.bias"], device)),
-                    wqkv=lin_w(torch.cat([sd[a + "q_proj.weight"], sd[a + "k_proj.weight"], sd[a + "v_proj.weight"]], 0), device),
-                    # the Q third of the bias carries the softmax scale * log2(e) that the projection's alpha puts on Q
-                    bqkv=vec(torch.cat([sd[a + "q_proj.bias"].float() * qs, sd[a + "k_proj.bias"].float(),
-                                        sd[a + "v_proj.bias"].float()], 0), device),
-                    wo=lin_w(sd[a + "out_proj.weight"], device), bo=vec(sd[a + "out_proj.bias"], device),
-                    w1=lin_w(sd[p + "mlp.fc1.weight"], device), b1=vec(sd[p + "mlp.fc1.bias"], device),
-                    w2=lin_w(sd[p + "mlp.fc2.weight"], device), b2=vec(sd[p + "mlp.fc2.bias"], device)))
-            self._w = w
-        self.device = device
-        return self
+    def _prepare(self, device):        # (the patch embedding is padded on the host)
+        c = self.config
+        sd = {k: _tower_key(self.state_dict_, k) for k in self._keys()}
+        D, K = c.hidden_size, 3 * c.patch_size ** 2
+        wp = torch.zeros((D, hip.patch_kpad(c.patch_size)), dtype=torch.float32)
+        wp[:, :K] = sd["embeddings.patch_embedding.weight"].float().reshape(D, K)
+        pos = sd["embeddings.position_embedding.weight"].float()
+        return {"patch": lin_w(wp, device),
+                # position embeddings of the patch tokens: the residual of the patch GEMM; class token row = class + position 0
+                "pos": pos[1:].contiguous().to(device, torch.bfloat16),
+                "cls": (sd["embeddings.class_embedding"].float() + pos[0]).to(device, torch.bfloat16),
+                "pre": (vec(sd["pre_layrnorm.weight"], device), vec(sd["pre_layrnorm.bias"], device)),
+                "post": (vec(sd["post_layernorm.weight"], device), vec(sd["post_layernorm.bias"], device)),
+                "proj": lin_w(sd["visual_projection.weight"], device),
+                "layers": [EncoderLayer(sd, f"encoder.layers.{i}.", device, c, c.layer_norm_eps) for i in range(c.num_hidden_layers)]}
 
     def _keys(self):
-        from .weights import SAFETY_HEAD_KEYS, vision_shapes
         return [k for k in vision_shapes(self.config) if k not in SAFETY_HEAD_KEYS]
 
     def _need_gpu(self, t: torch.Tensor):
-        from . import hip
         if self._w is None or not t.is_cuda:
             raise hip.SdvHipError("CLIPVisionEngine runs on the MI355X HIP path only (no CPU fallback): call .to('cuda') and "
                                   "pass GPU-resident tensors")
@@ -201,7 +171,6 @@ class CLIPVisionEngine:
         """Patch rows bf16 [n * (S/P)^2, Kpad] -> embeddings bf16 [n * Tpad, D] BEFORE pre_layrnorm: row 0 of every image's block
         is class_embedding + position 0, rows 1 ... T - 1 are patch GEMM (no bias) + position, rows T ... Tpad - 1 are left as
         ``out`` holds them (zeros when the buffer is allocated here)."""
-        from . import hip
         self._need_gpu(patches)
         c, w = self.config, self._w
         D, T, Tpad, NP = c.hidden_size, self.T, self.Tpad, self.T - 1
@@ -219,37 +188,27 @@ class CLIPVisionEngine:
     @torch.no_grad()
     def encode(self, x: torch.Tensor, n: int) -> torch.Tensor:
         """Embeddings bf16 [n * Tpad, D] (``embed``) -> image_embeds fp32 [n, projection_dim]."""
-        from . import hip
         self._need_gpu(x)
         c, w = self.config, self._w
         D, H, T, Tpad = c.hidden_size, c.num_attention_heads, self.T, self.Tpad
         dh = D // H
         if tuple(x.shape) != (n * Tpad, D) or not x.is_contiguous():
             raise hip.SdvHipError(f"CLIPVisionEngine: expected contiguous embeddings {(n * Tpad, D)}, got {tuple(x.shape)}")
-        epi = 4 if c.hidden_act == "quick_gelu" else 5
         eps = c.layer_norm_eps
-        x0, x = x, hip.layernorm(x, *w["pre"], eps=eps)
-        if TAP is not None:
-            TAP("pre_ln", {"x": x0, "out": x})
-        o = torch.zeros_like(x)          # (the attention writes the T real rows of every image; the pad rows stay zero)
-        for i, lw in enumerate(w["layers"]):
-            x0 = x
-            h = hip.layernorm(x, *lw["ln1"], eps=eps)
-            qkv = hip.linear(h, lw["wqkv"], lw["bqkv"], alpha=hip.q_prescale(dh), alpha_cols=D)   # [M, 3D] = [Q * qs | K | V]
-            for b in range(n):           # per image: Lq = Lk = T inside its Tpad-row block - pad rows never reach the softmax
+
+        def attend(qkv, o):              # per image: Lq = Lk = T inside its Tpad-row block - pad rows never reach the softmax
+            for b in range(n):
                 blk = qkv[b * Tpad:(b + 1) * Tpad]
                 hip.attention(blk, blk, blk, o[b * Tpad:(b + 1) * Tpad], B=1, H=H, Lq=T, Lk=T, dh=dh, ldq=3 * D, ldk=3 * D,
                               ldv=3 * D, ldo=D, scale=dh ** -0.5, k_off=D, v_off=2 * D, causal=False, q_prescaled=True,
                               v_rowmajor=True)
-            x = hip.linear(o, lw["wo"], lw["bo"], residual=x)
-            if TAP is not None:
-                TAP(f"layers.{i}.attn", {"x": x0, "out": x})
-            x0 = x
-            h = hip.layernorm(x, *lw["ln2"], eps=eps)
-            f = hip.linear(h, lw["w1"], lw["b1"], epi=epi)
-            x = hip.linear(f, lw["w2"], lw["b2"], residual=x)
-            if TAP is not None:
-                TAP(f"layers.{i}.mlp", {"x": x0, "out": x})
+
+        x0, x = x, hip.layernorm(x, *w["pre"], eps=eps)
+        if TAP is not None:
+            TAP("pre_ln", {"x": x0, "out": x})
+        o = torch.zeros_like(x)          # (the attention writes the T real rows of every image; the pad rows stay zero)
+        for i, layer in enumerate(w["layers"]):
+            x = layer(x, o, attend, TAP and (lambda name, xin, out: TAP(f"layers.{i}.{name}", {"x": xin, "out": out})))
         pooled = hip.layernorm(x.view(n, Tpad, D)[:, 0].contiguous(), *w["post"], eps=eps)        # class token only
         embeds = hip.linear_small(pooled.float(), w["proj"])                                      # fp32 [n, projection_dim]
         if TAP is not None:
@@ -286,11 +245,9 @@ class SafetyCheckerEngine:
         device = torch.device(device)
         if device.type != "cuda":
             if self._head is not None:
-                from . import hip
                 raise hip.SdvHipError("SafetyCheckerEngine cannot be moved off the GPU (no CPU fallback)")
             return self
         if self._head is None or device != self.device:
-            from .weights import vec
             self.vision.to(device)
             sd = self.state_dict_
             self._head = {"concept": vec(sd["concept_embeds"], device), "special": vec(sd["special_care_embeds"], device)}
@@ -301,7 +258,6 @@ class SafetyCheckerEngine:
         return self
 
     def _need_gpu(self, t):
-        from . import hip
         if self._head is None or not torch.is_tensor(t) or not t.is_cuda:
             raise hip.SdvHipError("SafetyCheckerEngine runs on the MI355X HIP path only (no CPU fallback): call .to('cuda') and "
                                   "pass GPU-resident uint8 frames")
@@ -309,7 +265,6 @@ class SafetyCheckerEngine:
     def preprocess(self, frames_u8: torch.Tensor) -> torch.Tensor:
         """uint8 NHWC frames in HBM -> patch rows (``hip.clip_preprocess_patches``); the tap tables are built on the host once per
         frame size and kept on the device."""
-        from . import hip
         self._need_gpu(frames_u8)
         c, fe = self.config, self.feature_extractor
         H, W = int(frames_u8.shape[1]), int(frames_u8.shape[2])
@@ -322,7 +277,6 @@ class SafetyCheckerEngine:
     @torch.no_grad()
     def screen(self, frames_u8: torch.Tensor):
         """-> (flags int32 [n], scores fp32 [n, 20]), both left on the device (nothing here synchronises with the host)."""
-        from . import hip
         self._need_gpu(frames_u8)
         n = frames_u8.shape[0]
         embeds = self.vision(self.preprocess(frames_u8), n)
@@ -332,7 +286,6 @@ class SafetyCheckerEngine:
     @torch.no_grad()
     def __call__(self, frames_u8: Optional[torch.Tensor] = None, *, images=None, clip_input=None):
         if images is not None:
-            from . import hip
             if self._head is None:
                 raise hip.SdvHipError("SafetyCheckerEngine runs on the MI355X HIP path only (no CPU fallback): call .to('cuda')")
             arr = np.asarray(images)
@@ -351,8 +304,6 @@ class SafetyCheckerEngine:
 def build_safety_checker(model_dir: Optional[Path] = None, seed: int = 0, cfg: Optional[VisionConfig] = None) -> SafetyCheckerEngine:
     """Real weights from ``<model_dir>/safety_checker`` when present (its ``config.json`` decides the architecture), otherwise the
     same architecture (``cfg``, default ViT-L/14) with seeded synthetic weights - flagged and logged, as the text encoder's are."""
-    from .config import vision_from_json
-    from .weights import load_safety_checker, synthetic_safety_checker, vision_shapes
     if model_dir is not None and (Path(model_dir) / "safety_checker" / "config.json").exists():
         cfg = vision_from_json(Path(model_dir) / "safety_checker" / "config.json")
         mean, std = CLIP_IMAGE_MEAN, CLIP_IMAGE_STD

@@ -1,17 +1,21 @@
-"""Launch traces of the UNet's transformer block and of whole UNet forwards: WHICH kernel runs, with which operands, at which size.
+"""Launch traces of the UNet's transformer block and of whole engine calls (UNet forward in bf16 and fp8, VAE decode, CLIP text and
+vision): WHICH kernel runs, with which operands, at which size.
 
 Every launch of the hot path is a ``torch.ops.sdv.k_*`` op with a Meta kernel, so an engine built with ``device="meta"`` runs its
 forward without a GPU and without the shared library, and a ``TorchDispatchMode`` sees every op it dispatches.  The trace of a case
 is the list of those ops: an ``sdv`` op with a canonical description of all its arguments (dtype / shape / stride / storage offset of
 every tensor, every integer, every float bit for bit), any other op by name - a ``copy_`` or ``cat`` that a change of the engine
 adds shows up like a changed launch does.  tests/golden/launch_trace.json holds, per case, the op names and a short hash of each
-launch's description (tests/golden/make_golden_launch_trace.py writes it, tests/test_launch_trace_cpu.py compares; one whole-engine
-case runs again on the device, tests/test_model_gpu.py).
+launch's description (tests/golden/make_golden_launch_trace.py writes it, tests/test_launch_trace_cpu.py compares; one case per
+engine runs again on the device, tests/test_model_gpu.py).  The CLIP engines check their inputs on the host before they launch
+anything, which a meta tensor cannot answer: their ``clip_call/*`` entries are recorded on the device, and the meta device runs the
+part behind those checks, whose ``sdv`` ops must be the entry's (``sdv_ops``).
 
 What the trace cannot see: WHICH tensor of a given dtype and shape an operand is - two same-shaped weights swapped leave it
 unchanged; the block-wise parity tests on the GPU catch that."""
 from __future__ import annotations
 
+import contextlib
 import hashlib
 import json
 import os
@@ -23,7 +27,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 from stable_diffusion_videos_amd import config as cfgs
 from stable_diffusion_videos_amd import engine as eng_mod
-from stable_diffusion_videos_amd import hip, weights
+from stable_diffusion_videos_amd import hip, text, vision, weights
 
 GOLDEN_FILE = Path(__file__).resolve().parent / "golden" / "launch_trace.json"
 BF16 = torch.bfloat16
@@ -109,6 +113,22 @@ CHUNKED = "c320_s16_chunk_2_of_4"                          # images [2, 4) of a 
 ENGINE_SIZES = ((2, 16, False, 0), (4, 16, True, 0), (6, 16, True, 512), (8, 64, True, 0))
 ENGINES = OrderedDict([("tiny", ENGINE_SIZES), ("sd14", ENGINE_SIZES), ("sd21", ENGINE_SIZES[3:])])
 UNET_CONFIGS = {"tiny": cfgs.tiny_unet, "sd14": cfgs.sd14_unet, "sd21": cfgs.sd21_unet}
+TILED = ("tiny", ENGINE_SIZES[1])                          # unet/<case>_tiled: circular padding in every conv
+# an fp8 UNetEngine with fixed scales (``on_meta`` stands in for the weight quantiser), and one forward that calibrates
+FP8_ENGINES = OrderedDict([("tiny", ENGINE_SIZES[1:3]), ("sd14", ENGINE_SIZES[1:3])])
+FP8_CALIBRATING = ("tiny", ENGINE_SIZES[1])                # unet_fp8/<case>_calibrating: one more bf16 GroupNorm per norm
+
+# VAEDecoderEngine.decode: (images, latent side, want_float, images per score chunk of the mid-block attention or 0, tiled)
+VAE_CONFIGS = {"tiny_vae": cfgs.tiny_vae, "sd_vae": cfgs.sd_vae}
+VAE_CASES = OrderedDict([("n1_s8", (1, 8, False, 0, False)),
+                         ("n3_s16_float", (3, 16, True, 0, False)),
+                         ("n3_s16_scorechunk2", (3, 16, False, 2, False)),      # chunks of 2 + 1 images: x_off / w_off / out_off
+                         ("n1_s8_tiled", (1, 8, False, 0, True))])
+
+# a whole text_encoder(ids) at L = 77 / vision(patches, n) call: (engine kind, config, batch)
+CLIP_CALLS = OrderedDict([("tiny_text_b2", ("text", cfgs.tiny_text, 2)),
+                          ("sd14_text_b1", ("text", cfgs.sd14_text, 1)),
+                          ("tiny_vision_n2", ("vision", cfgs.tiny_vision, 2))])
 
 
 def engine_case_name(arch, size):
@@ -118,9 +138,34 @@ def engine_case_name(arch, size):
 
 def _meta_state_dict(shapes):
     sd = OrderedDict((k, torch.empty(s, device="meta")) for k, s in shapes.items())
-    if "conv_in.weight" in sd:        # (weights.conv_w_c4 pads it on the host)
-        sd["conv_in.weight"] = torch.zeros(shapes["conv_in.weight"])
+    for k in ("conv_in.weight", "decoder.conv_in.weight", "embeddings.patch_embedding.weight"):        # (padded on the host)
+        if k in sd:
+            sd[k] = torch.zeros(shapes[k])
     return sd
+
+
+def _meta_quant_w(w):
+    """engine._quant_w without the amax it cannot read on meta: e4m3 bytes of w's shape and a scale that depends on the shape."""
+    return torch.empty(w.shape, dtype=hip.FP8, device=w.device), 2.0 ** -(6 + w.shape[0] // 64 % 3)
+
+
+def _meta_act_scale(y, prev):
+    """engine._act_scale likewise: a calibration sample's scale from its width, the running maximum kept."""
+    s = y.shape[1] / 8192.0
+    return s if prev is None else max(s, prev)
+
+
+@contextlib.contextmanager
+def on_meta():
+    """What an engine on the meta device cannot call, replaced while one is built or run there: ``hip.load`` (no library is needed)
+    and the two host-synchronising helpers of the fp8 mode."""
+    saved = [(hip, "load", hip.load), (eng_mod, "_quant_w", eng_mod._quant_w), (eng_mod, "_act_scale", eng_mod._act_scale)]
+    hip.load, eng_mod._quant_w, eng_mod._act_scale = (lambda *a, **k: None), _meta_quant_w, _meta_act_scale
+    try:
+        yield
+    finally:
+        for obj, attr, value in saved:
+            setattr(obj, attr, value)
 
 
 def trace_block(C, heads, side, nimg, shared, chunk_of=None):
@@ -159,13 +204,16 @@ def block_case_names():
     return (list(BLOCKS) + [CHUNKED] + [f"{k}@force6" for k in FORCED] + [f"{k}@{knob}=0" for k, knobs in KNOBS_OFF.items() for knob in knobs])
 
 
-def build_engine(arch, device):
-    """The UNetEngine of ``arch``: on "meta" from shapes alone (``hip.load`` must be patched out by the caller), on a GPU from the
-    seeded synthetic weights the parity tests use."""
+def build_engine(arch, device, tiled=False, fp8=False):
+    """The UNetEngine of ``arch``: on "meta" from shapes alone (inside ``on_meta``), on a GPU from the seeded synthetic weights the
+    parity tests use.  An fp8 engine gets fixed activation scales, different from one ResBlock to the next."""
     c = UNET_CONFIGS[arch]()
     shapes = weights.unet_shapes(c)
     sd = _meta_state_dict(shapes) if str(device) == "meta" else weights.synthetic_state_dict(shapes, seed=0)
-    return eng_mod.UNetEngine(c, sd, device)
+    engine = eng_mod.UNetEngine(c, sd, device, tiled=tiled, fp8=fp8)
+    if fp8:
+        engine.set_fp8_scales([(2.0 ** -(3 + i % 3), 2.0 ** -(4 + i % 2)) for i in range(len(engine.res))])
+    return engine
 
 
 def trace_engine(engine, nimg, side, cfg_shared, chunk_rows):
@@ -188,3 +236,75 @@ def trace_engine(engine, nimg, side, cfg_shared, chunk_rows):
         else:
             os.environ["SDV_CHUNK_ROWS"] = before
     return rec.trace
+
+
+def trace_engine_calibrating(arch, size):
+    """One forward of a fresh fp8 engine on meta (inside ``on_meta``) while ``fp8_calibration`` is on."""
+    c = UNET_CONFIGS[arch]()
+    engine = eng_mod.UNetEngine(c, _meta_state_dict(weights.unet_shapes(c)), "meta", fp8=True)
+    engine.fp8_calibration(True)
+    try:
+        return trace_engine(engine, *size)
+    finally:
+        engine.fp8_calibration(False)
+
+
+def build_vae(arch, device, tiled=False):
+    c = VAE_CONFIGS[arch]()
+    shapes = weights.vae_decoder_shapes(c)
+    sd = _meta_state_dict(shapes) if str(device) == "meta" else weights.synthetic_state_dict(shapes, seed=0)
+    return eng_mod.VAEDecoderEngine(c, sd, device, tiled=tiled)
+
+
+def trace_vae(engine, nimg, side, want_float, per_chunk):
+    """One decode of ``nimg`` latents of side x side; ``per_chunk`` images per score chunk of the mid-block attention (0: the engine's
+    own limit, which holds all of them)."""
+    lat = torch.zeros((nimg, side, side, engine.cfg.latent_channels), dtype=torch.float32, device=engine.device)
+    before = engine.score_chunk_bytes
+    if per_chunk:
+        engine.score_chunk_bytes = per_chunk * 6 * side ** 4
+    try:
+        with Recorder() as rec:
+            engine.decode(lat, want_float=want_float)
+    finally:
+        engine.score_chunk_bytes = before
+    return rec.trace
+
+
+def trace_clip_call(name, device):
+    """The whole call of a CLIP engine on a GPU - host-side checks included - on seeded synthetic weights."""
+    kind, cfg, n = CLIP_CALLS[name]
+    c = cfg()
+    if kind == "text":
+        engine = text.build_text_encoder(c, None, seed=0).to(device)
+        arg = (torch.arange(n * LC, device=device).reshape(n, LC) % c.vocab_size,)
+    else:
+        sd = weights.synthetic_safety_checker(c, seed=0)
+        engine = vision.CLIPVisionEngine(c, sd).to(device)
+        arg = (torch.zeros((n * (c.num_tokens - 1), hip.patch_kpad(c.patch_size)), dtype=BF16, device=device), n)
+    with Recorder() as rec:
+        engine(*arg)
+    return rec.trace
+
+
+def trace_clip_on_meta(name):
+    """The same call on the meta device (inside ``on_meta``), from shapes alone: the text engine from behind its id-range check,
+    the vision engine whole but for its residency check."""
+    kind, cfg, n = CLIP_CALLS[name]
+    c = cfg()
+    if kind == "text":
+        engine = text.CLIPTextEngine(c, _meta_state_dict(weights.clip_text_shapes(c)))
+        call, arg = engine._forward, (torch.empty((n, LC), dtype=torch.int64, device="meta"),)
+    else:
+        engine = vision.CLIPVisionEngine(c, _meta_state_dict(weights.vision_shapes(c)))
+        engine._need_gpu = lambda t: None
+        call, arg = engine, (torch.empty((n * (c.num_tokens - 1), hip.patch_kpad(c.patch_size)), dtype=BF16, device="meta"), n)
+    engine._w = engine._prepare("meta")
+    with Recorder() as rec:
+        call(*arg)
+    return rec.trace
+
+
+def sdv_ops(entry):
+    """The launches of a golden entry or of ``digest(trace)``, without the ops recorded by name only."""
+    return [(n, a) for n, a in zip(entry["ops"], entry["args"]) if "::" not in n]

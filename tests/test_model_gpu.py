@@ -560,6 +560,28 @@ def test_unet_launch_trace_on_the_device(hip, dev, arch):
     assert diff is None, diff
 
 
+def test_vae_launch_trace_on_the_device(hip, dev):
+    """A real tiny_vae decode of one image of 8 x 8 latents launches what the meta device's ``vae/*`` case pins."""
+    import launch_trace as lt
+    nimg, side, want_float, per_chunk, tiled = lt.VAE_CASES["n1_s8"]
+    want = json.loads(lt.GOLDEN_FILE.read_text())["vae/tiny_vae_n1_s8"]
+    trace = lt.trace_vae(lt.build_vae("tiny_vae", dev, tiled=tiled), nimg, side, want_float, per_chunk)
+    torch.cuda.synchronize()
+    diff = lt.first_difference(trace, want)
+    assert diff is None, diff
+
+
+@pytest.mark.parametrize("name", ["tiny_text_b2", "tiny_vision_n2"])
+def test_clip_call_launch_trace_on_the_device(hip, dev, name):
+    """The whole ``text_encoder(ids)`` / ``vision(patches, n)`` call, host-side checks included, is the recorded ``clip_call/*``."""
+    import launch_trace as lt
+    want = json.loads(lt.GOLDEN_FILE.read_text())["clip_call/" + name]
+    trace = lt.trace_clip_call(name, dev)
+    torch.cuda.synchronize()
+    diff = lt.first_difference(trace, want)
+    assert diff is None, diff
+
+
 @pytest.mark.parametrize("fp8", [False, True])
 def test_cache_blocked_forward(hip, dev, fp8, monkeypatch):
     """UNetEngine._segment walks a ResBlock (+ transformer) over the batch in cache-sized chunks of images.  Every op of those

@@ -37,14 +37,13 @@ for (n, x, gx), (_, y, gy) in zip(a, b):
 
 # ---- inside the first differing block: every intermediate (and the epilogue statistics) under both tile choices -------------------
 prev = dict((n, x) for n, x, _ in a)["decoder.up_blocks.2.resnets.2:resnet"]
-blk = pipe.vae.up[2]
-wu, bu = blk["up"]
-r = pipe.vae.up[3]["res"][0]
+up = pipe.vae.up[2].resample
+r = pipe.vae.up[3].res[0]
 nimg, H = 4, 64                      # tiny VAE: 16 -> 32 -> 64 -> 128; up_blocks.2's upsampler takes 64 x 64 to 128 x 128
 res = {}
 for tile in (0, 6):
     hip.FORCE_TILE = tile
-    x = hip.upconv3x3_phase(prev, wu, bu, nimg=nimg, H=H, W=H, gn=True)
+    x = hip.upconv3x3_phase(prev, up.w, up.b, nimg=nimg, H=H, W=H, gn=True)
     HW = 4 * H * H
     h1 = hip.groupnorm(x, r.g1, r.b1, nimg=nimg, HW=HW, groups=r.groups, eps=r.eps, silu=True)
     c1 = hip.conv3x3(h1, r.w1, r.c1_bias, nimg=nimg, H=2 * H, W=2 * H, gn=True)
