@@ -63,6 +63,17 @@ int sdv_abi_version(void);
  *           bias + (*step_ptr) * bias_step_stride (per-denoise-step time-embedding bias table).
  * zero_page unused since ABI v1 kernels zero-fill padding through the buffer-descriptor range check (may be NULL).
  * batch     blockIdx.z; element strides sX/sW/sC/sR (0 = shared).
+ * C / R     alignment of the bf16 output and the residual.  The epilogue has three store paths and picks one per launch:
+ *             staged       ldc % 8 == 0, N % 8 == 0 (GEGLU: N / 2), ldr % 8 == 0, sC % 8 == 0, sR % 8 == 0 and C, R and bias on
+ *                          16-byte addresses: whole 16-byte row segments.  A launch that misses one of these is NOT an error, it
+ *                          takes one of the two register-direct paths below;
+ *             8-byte       ldc % 4 == 0 (and ldr % 4 == 0 when there is a residual), and every GEGLU launch: four columns of C
+ *                          (and of R) move as ONE 8-byte access.  The kernel chooses this path from ldc / ldr alone, so this is a
+ *                          REQUIREMENT: C and R must then lie on 8-byte addresses, and sC / sR of a batched launch must be
+ *                          multiples of 4 elements.  sdv_gemm_bf16 refuses (SDV_ERR_ARG, nothing launched) a launch that breaks it;
+ *             scalar       any other ldc / ldr: element by element, C and R need their natural 2-byte alignment only.
+ *           The typed outputs (out_mode) need the natural alignment of their element; out_f32 moves as 16-byte pieces only where
+ *           the kernel finds ldc % 4 == 0, sC % 4 == 0 and a 16-byte address, element by element otherwise.
  * ------------------------------------------------------------------------------------------ */
 typedef struct sdv_gemm_args {
     const sdv_bf16* X;

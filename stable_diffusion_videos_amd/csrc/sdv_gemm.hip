@@ -1531,6 +1531,14 @@ static int sdv_gemm_impl(const sdv_gemm_args* args, void* stream, int plan) {
     if (plan == 2) return a.split_k;
     SDV_REQUIRE(!(a.epi >= 3 && tile >= 6 && tile <= 9), "sdv_gemm_bf16: epi %d is not available in the 8-wave tile %d", a.epi, tile);
     SDV_REQUIRE(!(a.epi == 1 && a.R), "sdv_gemm_bf16: GEGLU does not take a residual");
+    if (!a.out_mode && (a.epi == 1 || ((a.ldc & 3) == 0 && (!a.R || (a.ldr & 3) == 0)))) {
+        // sdv_hip.h "C / R": the register-direct epilogue picks its 8-byte accesses from ldc / ldr alone (and the GEGLU one always
+        // stores 8 bytes) - the pointers have to be what those leading dimensions promise
+        SDV_REQUIRE(((((uintptr_t)a.C) | ((uintptr_t)a.R)) & 7) == 0,
+                    "sdv_gemm_bf16: with ldc %% 4 == 0 (and ldr %% 4 == 0) C and R move as 8-byte pieces and must be 8-byte aligned");
+        SDV_REQUIRE(a.batch <= 1 || a.mode == 4 || ((a.sC | a.sR) & 3) == 0,
+                    "sdv_gemm_bf16: with ldc %% 4 == 0 (and ldr %% 4 == 0) the batch strides sC / sR must be multiples of 4 elements");
+    }
     auto run_tile = [&]() -> int {
     switch (tile) {
 #ifdef SDV_GEMM_ONLY_TILE6   // (tools: compile the 256 x 320 tile alone for resource / ISA inspection)

@@ -374,6 +374,8 @@ def gemm(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int,
          want_stats: bool = False, ln_eps: float = 1e-5, out_mode: int = 0, out_f32: Optional[torch.Tensor] = None,
          out_u8: Optional[torch.Tensor] = None, gn_hw: int = 0):
     """``sdv_gemm_bf16`` through ``torch.ops.sdv.k_igemm`` (element offsets x_off / w_off / out_off select sub-matrices).
+    ``out`` / ``residual`` may be windows of wider buffers; what alignment they need follows from ldc / ldr (sdv_hip.h "C / R":
+    ``sdv_gemm_bf16`` refuses a launch that breaks it - ``SdvHipError``, nothing launched).
     ``out_mode`` 1 / 2: fp32 output / image epilogue into ``out_f32`` / ``out_u8`` (``out`` may be None), see sdv_hip.h.
     ``ln=(stats, s)``: LayerNorm folded into this GEMM (sdv_hip.h): ``stats`` fp32 [rows, 2] = (mean, rstd) from
     ``want_stats`` of the producer, ``s`` fp32 row sums of the gamma-scaled weights.  ``want_stats=True`` returns the

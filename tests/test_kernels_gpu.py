@@ -1,6 +1,10 @@
 """Per-kernel parity of libsdv_hip.so (through the C ABI) against plain PyTorch fp32 references of the
 same op, on bf16-representable inputs.  Tolerances: elementwise kernels ~fp32 roundoff / 1 bf16 ulp;
-MFMA kernels (bf16 in, fp32 accumulate, bf16 out) rel-L2 <= 4e-3 against fp32 (SURVEY.md 8c ladder)."""
+MFMA kernels (bf16 in, fp32 accumulate, bf16 out) rel-L2 <= 4e-3 against fp32 (SURVEY.md 8c ladder).
+A rel-L2 gate does not see a single wrong pixel: the ragged ends of sdv_gemm_bf16 - conv seams and wraps, M / N tails, the staged /
+8-byte / scalar store paths, typed outputs, the persistent tile walk, split-K, fp8, the small-channel convs, on every tile - are
+gated element by element against float64, inside NaN guards, by test_igemm_edges_gpu.py (the attention kernels' by
+test_attention_edges_gpu.py)."""
 import math
 
 import numpy as np
