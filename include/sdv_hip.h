@@ -428,6 +428,37 @@ int sdv_jpeg_entropy_pack(const int16_t* coef, int32_t n, int32_t H, int32_t W, 
                           void* scratch, int64_t scratch_bytes, uint8_t* out, int64_t out_cap, int64_t* offsets, int64_t* needed,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PNG encoder (csrc/sdv_png.hip).  Replaces the host-side PNG compression of frames the GPU already holds: `image.save(frame_filepath)`
+ * in make_clip_frames for the default `.png` image_file_ext (stable_diffusion_pipeline.py:553).  Lossless; only compressed bytes
+ * leave HBM.
+ *
+ * Stream: signature | IHDR (8 bit RGB, no interlace) | ONE IDAT | IEND.  Every row = filter-type byte + 3W bytes; the type is chosen
+ * per row among all five by libpng's heuristic (minimum sum of v < 128 ? v : 256 - v over the filtered bytes, ties to the lowest
+ * type; row 0 sees a row of zeros above).  zlib: `78 01`; the filtered rows are cut into stripes of stripe_rows rows, each stripe is
+ * one dynamic-Huffman deflate block (BFINAL 0; literals and end-of-block only, no matches; HLIT 0, HDIST 0 with the one distance
+ * length 0, HCLEN 15 with code-length code lengths 0 for 16 / 17 / 18 and 4 for 0 .. 15, so the 258 lengths follow as plain 4-bit
+ * codes) and an empty stored block behind it, which pads to a byte: stripes are independent bit streams.  `03 00` (final fixed block,
+ * end-of-block only) and the Adler-32 end the stream.  Literal code lengths per stripe: a Huffman code of the stripe's histogram
+ * (end-of-block counts 1), limited to 15 bits where the tree is deeper, canonical codes (RFC 1951 3.2.2).
+ * The 4 bytes of the IDAT chunk's CRC are written as zeros: the caller computes the CRC-32 over tag + data on the host.
+ *
+ * sdv_png_filter_u8      frames uint8 RGB NHWC [n][H][W][3] contiguous -> filtered uint8 [n][H][1 + 3W] and adler_rows uint32 [n][H][2]:
+ *   per row (sum d_j, sum (R - j) d_j) mod 65521 over its R = 1 + 3W bytes, j = 0 .. R - 1.  One launch.
+ *
+ * sdv_png_deflate_pack   filtered (4-byte aligned) + adler_rows -> out: n complete files back to back, out[offsets[k] .. offsets[k + 1])
+ *   is file k; offsets int64 [n + 1] and needed int64 [1] (= offsets[n]) in GPU memory.  header: the 33 bytes signature + IHDR chunk
+ *   (GPU memory).  scratch: 8-byte aligned, at least 16 * S + 8 * ((n + 1) / 2) + 1040 * S bytes for S = n * ceil(H / stripe_rows)
+ *   stripes.  lengths: NULL or uint8 [n][ceil(H / stripe_rows)][257], receives the literal / end-of-block code lengths used.
+ *   When *needed > out_cap NOTHING is written to out (offsets, needed and lengths still are): the caller retries with *needed bytes.
+ *   Three launches on `stream`: count (one wave per stripe: histogram, code lengths, codes, byte length), scan (positions, Adler-32),
+ *   write (one wave per stripe, storing at the final positions).
+ * 1 <= H, W <= 16384, 1 <= n <= 65535, 1 <= stripe_rows <= H. */
+int sdv_png_filter_u8(const uint8_t* frames, int32_t n, int32_t H, int32_t W, uint8_t* filtered, uint32_t* adler_rows, void* stream);
+int sdv_png_deflate_pack(const uint8_t* filtered, const uint32_t* adler_rows, int32_t n, int32_t H, int32_t W, int32_t stripe_rows,
+                         const uint8_t* header, int32_t header_len, void* scratch, int64_t scratch_bytes, uint8_t* out,
+                         int64_t out_cap, int64_t* offsets, int64_t* needed, uint8_t* lengths, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,9 @@ _SIGNATURES = {
     "sdv_jpeg_transform_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.c_void_p, C.c_void_p]),
     "sdv_jpeg_entropy_pack": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdv_png_filter_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdv_png_deflate_pack": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1242,3 +1245,105 @@ def jpeg_entropy_pack(coef: torch.Tensor, H: int, W: int, header: torch.Tensor, 
     sdv_jpeg_entropy_pack): ``out[offsets[k]:offsets[k + 1]]`` is file k.  When ``needed`` (= offsets[n]) exceeds ``out.numel()``
     nothing was written to ``out``: call again with a buffer of that size."""
     _k_jpeg_entropy_pack(coef, int(H), int(W), header, scratch, out, offsets, needed)
+
+
+# ------------------------------------------------------------------------------------------------
+# PNG encoder (csrc/sdv_png.hip; png.py builds the header and the workspaces and fills the IDAT CRC)
+# ------------------------------------------------------------------------------------------------
+PNG_MAX_DIM = 16384
+
+
+def png_stripes(H: int, W: int, stripe_rows: Optional[int] = None) -> int:
+    """Deflate blocks per frame: the filtered rows are cut into stripes of ``stripe_rows`` rows (default: as many rows as fit 32 KiB)."""
+    if stripe_rows is None:
+        stripe_rows = max(1, min(H, 32768 // (1 + 3 * W)))
+    if not 1 <= stripe_rows <= H:
+        raise SdvHipError(f"png: stripe_rows must be 1 .. H = {H}, got {stripe_rows}")
+    return (H + stripe_rows - 1) // stripe_rows
+
+
+def png_scratch_bytes(n: int, H: int, stripe_rows: int) -> int:
+    """sdv_png_deflate_pack's scratch: an int64 position and an int64 length per stripe, an Adler-32 per frame, 260 code words per stripe."""
+    S = n * png_stripes(H, 1, stripe_rows)
+    return 16 * S + 8 * ((n + 1) // 2) + 1040 * S
+
+
+def _png_frame_shape(what, frames):
+    if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise SdvHipError(f"{what}: frames must be a contiguous uint8 [n, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)} "
+                          f"contiguous={frames.is_contiguous()}")
+    n, H, W, _ = frames.shape
+    if n < 1 or not (1 <= H <= PNG_MAX_DIM and 1 <= W <= PNG_MAX_DIM):
+        raise SdvHipError(f"{what}: frame size must be 1 .. {PNG_MAX_DIM} and n >= 1, got n={n} H={H} W={W}")
+    return n, H, W
+
+
+def _png_filter_impl(frames, filtered, adler_rows):
+    n, H, W = _png_frame_shape("png_filter", frames)
+    if filtered.dtype != torch.uint8 or tuple(filtered.shape) != (n, H, 1 + 3 * W) or not filtered.is_contiguous():
+        raise SdvHipError(f"png_filter: filtered must be a contiguous uint8 [{n}, {H}, {1 + 3 * W}] tensor, got {filtered.dtype} {tuple(filtered.shape)}")
+    if adler_rows.dtype != torch.int32 or tuple(adler_rows.shape) != (n, H, 2) or not adler_rows.is_contiguous():
+        raise SdvHipError(f"png_filter: adler_rows must be a contiguous int32 [{n}, {H}, 2] tensor, got {adler_rows.dtype} {tuple(adler_rows.shape)}")
+    lib = load()
+    args = (_ptr(frames, name="frames"), n, H, W, _ptr(filtered, name="filtered"), _ptr(adler_rows, name="adler_rows"))
+    _launch("png_filter", dict(bytes=2.0 * 3 * n * H * W), lambda: _check(lib.sdv_png_filter_u8(*args, _stream()), "sdv_png_filter_u8"))
+
+
+_k_png_filter = _defop("k_png_filter(Tensor frames, Tensor(a!) filtered, Tensor(b!) adler_rows) -> ()", _png_filter_impl)
+
+
+def png_filter(frames: torch.Tensor, filtered: Optional[torch.Tensor] = None, adler_rows: Optional[torch.Tensor] = None):
+    """uint8 RGB frames [n, H, W, 3] in HBM -> (filtered rows uint8 [n, H, 1 + 3W], Adler-32 partials int32 [n, H, 2])
+    (``torch.ops.sdv.k_png_filter`` -> sdv_png_filter_u8): per row the filter type libpng's heuristic picks among all five."""
+    n, H, W = _png_frame_shape("png_filter", frames)
+    if filtered is None:
+        filtered = torch.empty((n, H, 1 + 3 * W), dtype=torch.uint8, device=frames.device)
+    if adler_rows is None:
+        adler_rows = torch.empty((n, H, 2), dtype=torch.int32, device=frames.device)
+    _k_png_filter(frames, filtered, adler_rows)
+    return filtered, adler_rows
+
+
+def _png_deflate_pack_impl(filtered, adler_rows, stripe_rows, header, scratch, out, offsets, needed, lengths):
+    if filtered.dtype != torch.uint8 or filtered.ndim != 3 or filtered.shape[2] % 3 != 1 or filtered.shape[2] < 4 or not filtered.is_contiguous():
+        raise SdvHipError(f"png_deflate_pack: filtered must be a contiguous uint8 [n, H, 1 + 3W] tensor, got {filtered.dtype} {tuple(filtered.shape)}")
+    n, H, R = filtered.shape
+    W = (R - 1) // 3
+    if n < 1 or not (1 <= H <= PNG_MAX_DIM and 1 <= W <= PNG_MAX_DIM):
+        raise SdvHipError(f"png_deflate_pack: frame size must be 1 .. {PNG_MAX_DIM} and n >= 1, got n={n} H={H} W={W}")
+    if adler_rows.dtype != torch.int32 or tuple(adler_rows.shape) != (n, H, 2) or not adler_rows.is_contiguous():
+        raise SdvHipError(f"png_deflate_pack: adler_rows must be a contiguous int32 [{n}, {H}, 2] tensor, got {adler_rows.dtype} {tuple(adler_rows.shape)}")
+    stripes = png_stripes(H, W, stripe_rows)
+    for name, t in (("header", header), ("scratch", scratch), ("out", out)):
+        if t.dtype != torch.uint8 or t.ndim != 1 or not t.is_contiguous():
+            raise SdvHipError(f"png_deflate_pack: {name} must be a contiguous 1-D uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+    if header.numel() != 33:
+        raise SdvHipError(f"png_deflate_pack: header must hold the 33 bytes signature + IHDR chunk, got {header.numel()}")
+    if scratch.numel() < png_scratch_bytes(n, H, stripe_rows):
+        raise SdvHipError(f"png_deflate_pack: scratch holds {scratch.numel()} bytes, {n} frames of {stripes} stripes need "
+                          f"{png_scratch_bytes(n, H, stripe_rows)}")
+    if offsets.dtype != torch.int64 or offsets.numel() != n + 1 or not offsets.is_contiguous():
+        raise SdvHipError(f"png_deflate_pack: offsets must be a contiguous int64 vector of n + 1 = {n + 1} elements, got {offsets.dtype} x {offsets.numel()}")
+    if needed.dtype != torch.int64 or needed.numel() != 1:
+        raise SdvHipError(f"png_deflate_pack: needed must be one int64 element, got {needed.dtype} x {needed.numel()}")
+    if lengths is not None and (lengths.dtype != torch.uint8 or tuple(lengths.shape) != (n, stripes, 257) or not lengths.is_contiguous()):
+        raise SdvHipError(f"png_deflate_pack: lengths must be a contiguous uint8 [{n}, {stripes}, 257] tensor, got {lengths.dtype} {tuple(lengths.shape)}")
+    lib = load()
+    args = (_ptr(filtered, name="filtered"), _ptr(adler_rows, name="adler_rows"), n, H, W, stripe_rows, _ptr(header, name="header"), header.numel(),
+            _ptr(scratch, name="scratch"), scratch.numel(), _ptr(out, name="out"), out.numel(), _ptr(offsets, name="offsets"),
+            _ptr(needed, name="needed"), _ptr(lengths, name="lengths"))
+    _launch("png_deflate_pack", dict(bytes=3.0 * filtered.numel()),
+            lambda: _check(lib.sdv_png_deflate_pack(*args, _stream()), "sdv_png_deflate_pack"))
+
+
+_k_png_deflate_pack = _defop("k_png_deflate_pack(Tensor filtered, Tensor adler_rows, int stripe_rows, Tensor header, Tensor(a!) scratch, Tensor(b!) out, "
+                             "Tensor(c!) offsets, Tensor(d!) needed, Tensor(e!)? lengths) -> ()", _png_deflate_pack_impl)
+
+
+def png_deflate_pack(filtered: torch.Tensor, adler_rows: torch.Tensor, stripe_rows: int, header: torch.Tensor, scratch: torch.Tensor,
+                     out: torch.Tensor, offsets: torch.Tensor, needed: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+    """Huffman-code the filtered rows, one dynamic block per stripe, and pack complete PNG files into ``out``
+    (``torch.ops.sdv.k_png_deflate_pack`` -> sdv_png_deflate_pack): ``out[offsets[k]:offsets[k + 1]]`` is file k with four zero bytes
+    where the IDAT CRC goes.  When ``needed`` (= offsets[n]) exceeds ``out.numel()`` nothing was written to ``out``: call again with
+    a buffer of that size.  ``lengths`` (uint8 [n, stripes, 257]) receives the code lengths of every stripe."""
+    _k_png_deflate_pack(filtered, adler_rows, int(stripe_rows), header, scratch, out, offsets, needed, lengths)

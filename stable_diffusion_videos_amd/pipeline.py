@@ -117,6 +117,7 @@ class StableDiffusionWalkPipeline:
         self.tiled = False
         self.upsampler = None
         self.jpeg_quality = 75             # output_type="jpeg" and .jpg / .jpeg frame files (what PIL's Image.save writes for them)
+        self.png_encoder = "pil"           # .png frame files: "pil" = Image.save on the host, "hip" = compressed in HBM (png.py); SDV_PNG wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
@@ -555,8 +556,9 @@ class StableDiffusionWalkPipeline:
         if kwargs.get("return_latents", False):
             return hip.nhwc_to_nchw(ent.latents)[:B_real]
         # "numpy_u8": rounded uint8 NHWC array, no PIL objects; "u8_cuda": the same array left in HBM (upsampler input);
-        # "jpeg": list[bytes], each a complete JFIF file compressed on the GPU (jpeg.py) - only compressed bytes cross to the host
-        want_float = output_type not in ("pil", "numpy_u8", "u8_cuda", "jpeg")
+        # "jpeg": list[bytes], each a complete JFIF file compressed on the GPU (jpeg.py) - only compressed bytes cross to the host;
+        # "png": the same with complete PNG files (png.py), lossless
+        want_float = output_type not in ("pil", "numpy_u8", "u8_cuda", "jpeg", "png")
         u8, f32 = self.vae.decode(ent.latents, want_float=want_float)                            # :432-435
         flags_host = None
         if self.safety_checker is not None:                                                       # :440-447
@@ -573,6 +575,9 @@ class StableDiffusionWalkPipeline:
         elif output_type == "jpeg":                                                               # (after the black-out above)
             from .jpeg import encoder_for
             image = encoder_for(self.jpeg_quality, u8.device).encode(u8[:B_real])
+        elif output_type == "png":
+            from .png import encoder_for
+            image = encoder_for(u8.device).encode(u8[:B_real])
         elif want_float:
             image = f32[:B_real].cpu().numpy()                                                    # :438
         else:
@@ -619,6 +624,13 @@ class StableDiffusionWalkPipeline:
             yield batch_idx, embeds, noise.view(n, Cc, hh, ww)
             batch_idx += 1
 
+    def png_encoder_choice(self) -> str:
+        """Who compresses ``.png`` frame files: the environment variable SDV_PNG when it is set, else ``self.png_encoder``."""
+        choice = (os.environ.get("SDV_PNG") or self.png_encoder).lower()
+        if choice not in ("pil", "hip"):
+            raise ValueError(f"SDV_PNG / png_encoder must be 'pil' or 'hip', got {choice!r}")
+        return choice
+
     def make_clip_frames(self, prompt_a: str, prompt_b: str, seed_a: int, seed_b: int, num_interpolation_steps: int = 5,
                          save_path: Union[str, Path] = "outputs/", num_inference_steps: int = 50,
                          guidance_scale: float = 7.5, eta: float = 0.0, height: Optional[int] = None,
@@ -655,6 +667,10 @@ class StableDiffusionWalkPipeline:
         # .jpg / .jpeg frames are compressed on the GPU at the quality and subsampling Image.save uses for these extensions (75, 4:2:0);
         # SDV_JPEG=pil keeps the host-side PIL encode.  Every other extension is untouched.
         gpu_jpeg = image_file_ext.lower() in (".jpg", ".jpeg") and os.environ.get("SDV_JPEG", "hip").lower() != "pil"
+        # .png frames: self.png_encoder / SDV_PNG = "hip" compresses them on the GPU as well (png.py: lossless, the same pixels in a
+        # different byte stream); the default "pil" leaves every launch and every file byte as it was
+        gpu_png = image_file_ext.lower() == ".png" and self.png_encoder_choice() == "hip"
+        gpu_files = gpu_jpeg or gpu_png
         pos = 0
         for batch_idx, embeds_batch, noise_batch in batch_generator:
             frame_index = indices[pos]
@@ -665,12 +681,17 @@ class StableDiffusionWalkPipeline:
             logger.info(f"{log_prefix}[{batch_idx}/{num_batches}] {msg}")
             outputs = self(latents=noise_batch, text_embeddings=embeds_batch, height=height, width=width,
                            guidance_scale=guidance_scale, eta=eta, num_inference_steps=num_inference_steps,
-                           output_type="u8_cuda" if (upsample or gpu_jpeg) else "pil", negative_prompt=negative_prompt)["images"]
-            if gpu_jpeg:
-                from .jpeg import encoder_for
+                           output_type="u8_cuda" if (upsample or gpu_files) else "pil", negative_prompt=negative_prompt)["images"]
+            if gpu_files:
                 if upsample:
                     outputs = self.upsampler.upsample_u8(outputs)
-                for data in encoder_for(self.jpeg_quality, outputs.device).encode(outputs):
+                if gpu_jpeg:
+                    from .jpeg import encoder_for
+                    encoder = encoder_for(self.jpeg_quality, outputs.device)
+                else:
+                    from .png import encoder_for as png_encoder_for
+                    encoder = png_encoder_for(outputs.device)
+                for data in encoder.encode(outputs):
                     writer.submit_bytes(data, save_path / (f"frame%06d{image_file_ext}" % indices[pos]))
                     pos += 1
                 continue

@@ -93,7 +93,7 @@ class FrameWriter:
         os.replace(tmp, path)
 
     def submit_bytes(self, data: bytes, path: Path):
-        """A frame that is already an encoded file (jpeg.py: compressed on the GPU): same ``.part``-then-rename rule as ``submit``."""
+        """A frame that is already an encoded file (jpeg.py / png.py: compressed on the GPU): same ``.part``-then-rename rule as ``submit``."""
         self.pending.append(self.pool.submit(self._save_bytes, data, path))
 
     def drain(self):
