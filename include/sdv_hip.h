@@ -158,9 +158,12 @@ int sdv_gemm_split_k(const sdv_gemm_args* args);
  * first K slab prefetched behind the current tile's epilogue.  sdv_gemm_set_persistent(0) falls back to one workgroup per
  * tile (bit-identical results; for A/B timing in tools/).  Returns the previous setting. */
 int sdv_gemm_set_persistent(int on);
-/* > 0: at most n persistent workgroups per launch (default: one per CU).  Test / tools knob: with a small limit even a
- * 32-tile problem WALKS tiles, so the tile-walk path (next tile's first K slab behind the epilogue) can be put under the
- * oracle-based parity gates at sizes the CPU oracle finishes in seconds.  Returns the previous setting. */
+/* > 0: at most n persistent workgroups per launch (default: one per CU).  It caps EVERY persistent kernel: the 8-wave tiles of
+ * sdv_gemm_bf16 and the panel kernels of sdv_ffn_geglu_bf16 / sdv_linear320_bf16 / sdv_linear640_bf16 (one workgroup per 128-row
+ * panel, at most one per CU).  Test / tools knob: with a small limit even a 32-tile problem - or a few hundred rows of a panel
+ * kernel - WALKS tiles / panels, so the walk paths (next tile's first K slab behind the epilogue; the panel hand-over) can be put
+ * under the oracle-based parity gates at sizes the CPU oracle finishes in seconds.  Results are bit-identical: the limit only
+ * changes which workgroup computes a tile.  Returns the previous setting. */
 int sdv_gemm_set_grid_limit(int n);
 /* partial (sum, sumsq) [rows][slots][2] -> (mean, rstd) [rows][2] over C channels */
 int sdv_rowstats_finalize(const float* partials, int64_t rows, int32_t slots, int32_t C, float eps, float* out, void* stream);
@@ -202,7 +205,11 @@ int sdv_ffn_geglu_bf16(const sdv_bf16* X, const float* ln_stats, int64_t M, int3
  *            softmax scale * log2 e: sdv_attention_bf16 q_prescaled)
  *   R        [M][ldr] bf16 residual or NULL;  out [M][ldo] bf16
  *   stats_out [M][2] fp32 or NULL (N = 320): (mean, rstd = rsqrt(var + eps)) of the STORED rows - what the next LayerNorm fold
- *            (ln_stats of a later call, sdv_gemm_args.ln_stats) consumes; no partial sums, no sdv_rowstats_finalize launch
+ *            (ln_stats of a later call, sdv_gemm_args.ln_stats) consumes; no partial sums, no sdv_rowstats_finalize launch.
+ *            One pass in fp32, var = max(E[y^2] - mean^2, 0): the variance carries an error of up to 1e-5 E[y^2], so for rows with
+ *            a high |mean| / sigma the consumer's fold receives an rstd that is off by about half of 1e-5 E[y^2] / (var + eps)
+ *            (measured, tests/test_panel_edges_gpu.py: below 1e-3 for |mean| > 10 sigma rows of the residual stream, 75 % for a
+ *            constant row of 100s, whose true variance is 0)
  *   Vt       NULL, or (N = 960) [M / hw][320][ldvt] bf16: the LAST block of 320 columns - V of the fused Q K V projection - is stored
  *            TRANSPOSED per sample of hw tokens (hw % 128 == 0, M % hw == 0, ldvt >= hw), as sdv_attention_bf16 takes it with
  *            v_rowmajor = 0, and `out` ([M][ldo], ldo >= 640) receives only [Q | K] */

@@ -103,6 +103,9 @@ SDV_DEVICE float wave_max(float v) {
 
 // ---- host side error plumbing ------------------------------------------------------------------
 __attribute__((visibility("hidden"))) void sdv_set_error(const char* fmt, ...);   // (internal: not part of the C ABI)
+// sdv_gemm_set_grid_limit()'s current value (0 = no cap): every persistent launch - the igemm's 8-wave tiles, the panel kernels of
+// sdv_ffn.hip - starts at most that many workgroups (internal: defined in sdv_gemm.hip)
+__attribute__((visibility("hidden"))) int sdv_grid_limit();
 #define SDV_REQUIRE(cond, ...)            \
     do {                                  \
         if (!(cond)) {                    \

@@ -781,6 +781,14 @@ __global__ __launch_bounds__(256, 1) void panel_linear_kernel(const lin_args p) 
 
 }  // namespace
 
+// workgroups of a panel launch: one per panel, at most one per CU - and at most sdv_gemm_set_grid_limit() of them (tests: a small
+// limit makes a few hundred rows WALK panels; the kernels stride by gridDim.x)
+static int panel_grid(int npanels, int cus) {
+    const int limit = sdv_grid_limit();
+    const int grid = npanels < cus ? npanels : cus;
+    return limit > 0 && limit < grid ? limit : grid;
+}
+
 // C ABI: sdv_hip.h
 extern "C" int sdv_ffn_geglu_bf16(const sdv_bf16* X, const float* ln_stats, int64_t M, int32_t C, int32_t ldx, const sdv_bf16* W1, const sdv_bf16* W1x,
                                   const sdv_bf16* W2p, const float* bias2, sdv_bf16* out, int32_t ldo, void* stream) {
@@ -805,7 +813,7 @@ extern "C" int sdv_ffn_geglu_bf16(const sdv_bf16* X, const float* ln_stats, int6
     }
     const int npanels = (int)((M + 127) >> 7);
     ffn_args a{X, W1, W1x, W2p, bias2, ln_stats, out, M, ldx, ldo};
-    hipLaunchKernelGGL(ffn_geglu_kernel, dim3((unsigned)(npanels < cus[dev] ? npanels : cus[dev])), dim3(256), FFN_LDS, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ffn_geglu_kernel, dim3((unsigned)panel_grid(npanels, cus[dev])), dim3(256), FFN_LDS, (hipStream_t)stream, a);
     SDV_CHECK_LAUNCH("sdv_ffn_geglu_bf16");
     return SDV_OK;
 }
@@ -842,7 +850,7 @@ static int panel_linear_launch(const char* who, int K, const sdv_bf16* X, int64_
         }
         const int npanels = (int)((M + 127) >> 7);
         lin_args a{X, W, Wx, ln_stats, alpha, R, out, stats_out, Vt, M, ldx, ldr, ldo, ldvt, hw, eps};
-        hipLaunchKernelGGL(kern, dim3((unsigned)(npanels < cus[dev] ? npanels : cus[dev])), dim3(256), LIN_LDS, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(kern, dim3((unsigned)panel_grid(npanels, cus[dev])), dim3(256), LIN_LDS, (hipStream_t)stream, a);
     };
     if (K == FC) {
         if (N == FC) {

@@ -1372,6 +1372,8 @@ extern "C" int sdv_gemm_set_grid_limit(int n) {
     return prev;
 }
 
+int sdv_grid_limit() { return g_grid_limit; }
+
 static int sdv_gemm_impl(const sdv_gemm_args* args, void* stream, int plan) {
     SDV_REQUIRE(args != nullptr, "sdv_gemm_bf16: null args");
     sdv_gemm_args a = *args;
