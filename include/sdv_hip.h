@@ -448,7 +448,8 @@ int sdv_jpeg_entropy_pack(const int16_t* coef, int32_t n, int32_t H, int32_t W, 
  * codes) and an empty stored block behind it, which pads to a byte: stripes are independent bit streams.  `03 00` (final fixed block,
  * end-of-block only) and the Adler-32 end the stream.  Literal code lengths per stripe: a Huffman code of the stripe's histogram
  * (end-of-block counts 1), limited to 15 bits where the tree is deeper, canonical codes (RFC 1951 3.2.2).
- * The 4 bytes of the IDAT chunk's CRC are written as zeros: the caller computes the CRC-32 over tag + data on the host.
+ * The 4 bytes of the IDAT chunk's CRC are written as zeros: the caller computes the CRC-32 over tag + data on the host, or calls
+ * sdv_png_crc32.
  *
  * sdv_png_filter_u8      frames uint8 RGB NHWC [n][H][W][3] contiguous -> filtered uint8 [n][H][1 + 3W] and adler_rows uint32 [n][H][2]:
  *   per row (sum d_j, sum (R - j) d_j) mod 65521 over its R = 1 + 3W bytes, j = 0 .. R - 1.  One launch.
@@ -460,11 +461,46 @@ int sdv_jpeg_entropy_pack(const int16_t* coef, int32_t n, int32_t H, int32_t W, 
  *   When *needed > out_cap NOTHING is written to out (offsets, needed and lengths still are): the caller retries with *needed bytes.
  *   Three launches on `stream`: count (one wave per stripe: histogram, code lengths, codes, byte length), scan (positions, Adler-32),
  *   write (one wave per stripe, storing at the final positions).
- * 1 <= H, W <= 16384, 1 <= n <= 65535, 1 <= stripe_rows <= H. */
+ * 1 <= H, W <= 16384, 1 <= n <= 65535, 1 <= stripe_rows <= H.
+ *
+ * Matching mode (opt-in; additive, the version stays 12).  Container, filtering, Adler-32, `78 01`, the stripes, the empty stored
+ * block behind each, `03 00` and one dynamic block per stripe are as above; only the inside of a stripe's block changes.  For one
+ * stripe with bytes s[0 .. L), R = 1 + 3W:
+ *   prices      l0[v]: the 257 code lengths of the Huffman-only code of this stripe (what sdv_png_deflate_pack would use).
+ *   candidates  at position i with i + 3 <= L; every distance d has 1 <= d <= i and d <= 32768: the fixed distances 1, 2, 3, 4, 6,
+ *               R - 3, R, R + 3, and one hash candidate d = i - j, j the LARGEST position with j < 64 * (i / 64), j + 3 <= L and
+ *               h(j) == h(i), h(p) = ((s[p] | s[p+1] << 8 | s[p+2] << 16) * 0x9E3779B1 mod 2^32) >> 20 (12 bits): the hash sees only
+ *               positions of earlier 64-position groups.
+ *   length      the common prefix of s[i ..] and s[i - d ..] (overlap allowed), at most min(258, L - i); the best candidate is the
+ *               longest, ties go to the smaller d.
+ *   acceptance  a best match of length len >= 3 is taken iff  sum(l0[s[i + k]], k < len) > 12 + length extra bits + distance extra
+ *               bits  (RFC 1951 3.2.5).
+ *   parse       greedy from i = 0: an accepted match advances by len, else the literal by 1.  No match reaches outside its stripe.
+ *   block       no accepted match in the stripe: the block of sdv_png_deflate_pack, byte for byte.  Else BFINAL 0, BTYPE 10,
+ *               HLIT 29, HDIST 29, HCLEN 15, the same 19 code-length code lengths, 286 + 30 lengths as plain 4-bit codes, the
+ *               tokens, end-of-block.  Literal / length code: Huffman of the token histogram over 286 symbols (end-of-block counts
+ *               1); distance code: the same over 30 symbols, a single used symbol gets length 1; both limited to 15 bits.
+ *
+ * sdv_png_deflate_lz_pack  sdv_png_deflate_pack's arguments and contract (lengths: the PRICES l0), and: lz_scratch, 8-byte aligned, at
+ *   least 4 * n H R + 8 * ((S + 1) / 2) + 1280 * S bytes: first the tokens, uint32 [n H R], a stripe's tokens from the index of its
+ *   first filtered byte (len << 16 | dist for a match, the byte for a literal), then the token count of every stripe, uint32 [S],
+ *   then code words.  ll_lengths / d_lengths: NULL or uint8 [n][stripes][286] / [n][stripes][30], the final code lengths of every
+ *   stripe (a stripe without a match: l0 and zeros).  Six launches: count, match (one wave per stripe, 64 positions at a time),
+ *   token count, scan, write (stripes without a match), token write.
+ *
+ * sdv_png_crc32            the CRC-32 (zlib's) of every file's IDAT tag + data, out[offsets[k] + 37 .. offsets[k + 1] - 16), stored
+ *   big-endian into the 4-byte hole behind it.  offsets / needed: what a packer left in GPU memory; does nothing when
+ *   *needed > out_cap.  acc: uint32 [n] workspace.  A memset and two launches: 256-byte chunks, each shifted to its place by
+ *   x^(8 * bytes behind it) mod P and XOR-ed into its file's accumulator; then the preset and final-inversion terms and the store. */
 int sdv_png_filter_u8(const uint8_t* frames, int32_t n, int32_t H, int32_t W, uint8_t* filtered, uint32_t* adler_rows, void* stream);
 int sdv_png_deflate_pack(const uint8_t* filtered, const uint32_t* adler_rows, int32_t n, int32_t H, int32_t W, int32_t stripe_rows,
                          const uint8_t* header, int32_t header_len, void* scratch, int64_t scratch_bytes, uint8_t* out,
                          int64_t out_cap, int64_t* offsets, int64_t* needed, uint8_t* lengths, void* stream);
+int sdv_png_deflate_lz_pack(const uint8_t* filtered, const uint32_t* adler_rows, int32_t n, int32_t H, int32_t W, int32_t stripe_rows,
+                            const uint8_t* header, int32_t header_len, void* scratch, int64_t scratch_bytes, uint8_t* out,
+                            int64_t out_cap, int64_t* offsets, int64_t* needed, uint8_t* lengths, void* lz_scratch,
+                            int64_t lz_scratch_bytes, uint8_t* ll_lengths, uint8_t* d_lengths, void* stream);
+int sdv_png_crc32(uint8_t* out, int64_t out_cap, const int64_t* offsets, const int64_t* needed, int32_t n, uint32_t* acc, void* stream);
 
 #ifdef __cplusplus
 }

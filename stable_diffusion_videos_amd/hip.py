@@ -99,6 +99,10 @@ _SIGNATURES = {
     "sdv_png_filter_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdv_png_deflate_pack": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdv_png_deflate_lz_pack": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "sdv_png_crc32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1304,34 +1308,44 @@ def png_filter(frames: torch.Tensor, filtered: Optional[torch.Tensor] = None, ad
     return filtered, adler_rows
 
 
-def _png_deflate_pack_impl(filtered, adler_rows, stripe_rows, header, scratch, out, offsets, needed, lengths):
+def _png_pack_args(what, filtered, adler_rows, stripe_rows, header, scratch, out, offsets, needed, lengths):
+    """The checks both packers share -> (n, H, W, stripes, the C arguments up to ``lengths``)."""
     if filtered.dtype != torch.uint8 or filtered.ndim != 3 or filtered.shape[2] % 3 != 1 or filtered.shape[2] < 4 or not filtered.is_contiguous():
-        raise SdvHipError(f"png_deflate_pack: filtered must be a contiguous uint8 [n, H, 1 + 3W] tensor, got {filtered.dtype} {tuple(filtered.shape)}")
+        raise SdvHipError(f"{what}: filtered must be a contiguous uint8 [n, H, 1 + 3W] tensor, got {filtered.dtype} {tuple(filtered.shape)}")
     n, H, R = filtered.shape
     W = (R - 1) // 3
     if n < 1 or not (1 <= H <= PNG_MAX_DIM and 1 <= W <= PNG_MAX_DIM):
-        raise SdvHipError(f"png_deflate_pack: frame size must be 1 .. {PNG_MAX_DIM} and n >= 1, got n={n} H={H} W={W}")
+        raise SdvHipError(f"{what}: frame size must be 1 .. {PNG_MAX_DIM} and n >= 1, got n={n} H={H} W={W}")
     if adler_rows.dtype != torch.int32 or tuple(adler_rows.shape) != (n, H, 2) or not adler_rows.is_contiguous():
-        raise SdvHipError(f"png_deflate_pack: adler_rows must be a contiguous int32 [{n}, {H}, 2] tensor, got {adler_rows.dtype} {tuple(adler_rows.shape)}")
+        raise SdvHipError(f"{what}: adler_rows must be a contiguous int32 [{n}, {H}, 2] tensor, got {adler_rows.dtype} {tuple(adler_rows.shape)}")
     stripes = png_stripes(H, W, stripe_rows)
     for name, t in (("header", header), ("scratch", scratch), ("out", out)):
         if t.dtype != torch.uint8 or t.ndim != 1 or not t.is_contiguous():
-            raise SdvHipError(f"png_deflate_pack: {name} must be a contiguous 1-D uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+            raise SdvHipError(f"{what}: {name} must be a contiguous 1-D uint8 tensor, got {t.dtype} {tuple(t.shape)}")
     if header.numel() != 33:
-        raise SdvHipError(f"png_deflate_pack: header must hold the 33 bytes signature + IHDR chunk, got {header.numel()}")
+        raise SdvHipError(f"{what}: header must hold the 33 bytes signature + IHDR chunk, got {header.numel()}")
     if scratch.numel() < png_scratch_bytes(n, H, stripe_rows):
-        raise SdvHipError(f"png_deflate_pack: scratch holds {scratch.numel()} bytes, {n} frames of {stripes} stripes need "
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n} frames of {stripes} stripes need "
                           f"{png_scratch_bytes(n, H, stripe_rows)}")
     if offsets.dtype != torch.int64 or offsets.numel() != n + 1 or not offsets.is_contiguous():
-        raise SdvHipError(f"png_deflate_pack: offsets must be a contiguous int64 vector of n + 1 = {n + 1} elements, got {offsets.dtype} x {offsets.numel()}")
+        raise SdvHipError(f"{what}: offsets must be a contiguous int64 vector of n + 1 = {n + 1} elements, got {offsets.dtype} x {offsets.numel()}")
     if needed.dtype != torch.int64 or needed.numel() != 1:
-        raise SdvHipError(f"png_deflate_pack: needed must be one int64 element, got {needed.dtype} x {needed.numel()}")
+        raise SdvHipError(f"{what}: needed must be one int64 element, got {needed.dtype} x {needed.numel()}")
     if lengths is not None and (lengths.dtype != torch.uint8 or tuple(lengths.shape) != (n, stripes, 257) or not lengths.is_contiguous()):
-        raise SdvHipError(f"png_deflate_pack: lengths must be a contiguous uint8 [{n}, {stripes}, 257] tensor, got {lengths.dtype} {tuple(lengths.shape)}")
-    lib = load()
-    args = (_ptr(filtered, name="filtered"), _ptr(adler_rows, name="adler_rows"), n, H, W, stripe_rows, _ptr(header, name="header"), header.numel(),
+        raise SdvHipError(f"{what}: lengths must be a contiguous uint8 [{n}, {stripes}, 257] tensor, got {lengths.dtype} {tuple(lengths.shape)}")
+    return n, H, W, stripes
+
+
+def _png_pack_pointers(filtered, adler_rows, n, H, W, stripe_rows, header, scratch, out, offsets, needed, lengths):
+    return (_ptr(filtered, name="filtered"), _ptr(adler_rows, name="adler_rows"), n, H, W, stripe_rows, _ptr(header, name="header"), header.numel(),
             _ptr(scratch, name="scratch"), scratch.numel(), _ptr(out, name="out"), out.numel(), _ptr(offsets, name="offsets"),
             _ptr(needed, name="needed"), _ptr(lengths, name="lengths"))
+
+
+def _png_deflate_pack_impl(filtered, adler_rows, stripe_rows, header, scratch, out, offsets, needed, lengths):
+    n, H, W, _ = _png_pack_args("png_deflate_pack", filtered, adler_rows, stripe_rows, header, scratch, out, offsets, needed, lengths)
+    lib = load()
+    args = _png_pack_pointers(filtered, adler_rows, n, H, W, stripe_rows, header, scratch, out, offsets, needed, lengths)
     _launch("png_deflate_pack", dict(bytes=3.0 * filtered.numel()),
             lambda: _check(lib.sdv_png_deflate_pack(*args, _stream()), "sdv_png_deflate_pack"))
 
@@ -1347,3 +1361,66 @@ def png_deflate_pack(filtered: torch.Tensor, adler_rows: torch.Tensor, stripe_ro
     where the IDAT CRC goes.  When ``needed`` (= offsets[n]) exceeds ``out.numel()`` nothing was written to ``out``: call again with
     a buffer of that size.  ``lengths`` (uint8 [n, stripes, 257]) receives the code lengths of every stripe."""
     _k_png_deflate_pack(filtered, adler_rows, int(stripe_rows), header, scratch, out, offsets, needed, lengths)
+
+
+def png_lz_scratch_bytes(n: int, H: int, W: int, stripe_rows: int) -> int:
+    """sdv_png_deflate_lz_pack's token scratch: a uint32 token per filtered byte, a uint32 count per stripe, 320 code words per stripe."""
+    S = n * png_stripes(H, 1, stripe_rows)
+    return 4 * n * H * (1 + 3 * W) + 8 * ((S + 1) // 2) + 1280 * S
+
+
+def _png_deflate_lz_pack_impl(filtered, adler_rows, stripe_rows, header, scratch, out, offsets, needed, lz_scratch, lengths, ll_lengths, d_lengths):
+    what = "png_deflate_lz_pack"
+    n, H, W, stripes = _png_pack_args(what, filtered, adler_rows, stripe_rows, header, scratch, out, offsets, needed, lengths)
+    if lz_scratch.dtype != torch.uint8 or lz_scratch.ndim != 1 or not lz_scratch.is_contiguous():
+        raise SdvHipError(f"{what}: lz_scratch must be a contiguous 1-D uint8 tensor, got {lz_scratch.dtype} {tuple(lz_scratch.shape)}")
+    if lz_scratch.numel() < png_lz_scratch_bytes(n, H, W, stripe_rows):
+        raise SdvHipError(f"{what}: lz_scratch holds {lz_scratch.numel()} bytes, {n * H * (1 + 3 * W)} filtered bytes in {n * stripes} stripes need "
+                          f"{png_lz_scratch_bytes(n, H, W, stripe_rows)}")
+    for name, t, syms in (("ll_lengths", ll_lengths, 286), ("d_lengths", d_lengths, 30)):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (n, stripes, syms) or not t.is_contiguous()):
+            raise SdvHipError(f"{what}: {name} must be a contiguous uint8 [{n}, {stripes}, {syms}] tensor, got {t.dtype} {tuple(t.shape)}")
+    lib = load()
+    args = _png_pack_pointers(filtered, adler_rows, n, H, W, stripe_rows, header, scratch, out, offsets, needed, lengths) + (
+        _ptr(lz_scratch, name="lz_scratch"), lz_scratch.numel(), _ptr(ll_lengths, name="ll_lengths"), _ptr(d_lengths, name="d_lengths"))
+    _launch(what, dict(bytes=11.0 * filtered.numel()), lambda: _check(lib.sdv_png_deflate_lz_pack(*args, _stream()), "sdv_png_deflate_lz_pack"))
+
+
+_k_png_deflate_lz_pack = _defop("k_png_deflate_lz_pack(Tensor filtered, Tensor adler_rows, int stripe_rows, Tensor header, Tensor(a!) scratch, "
+                                "Tensor(b!) out, Tensor(c!) offsets, Tensor(d!) needed, Tensor(e!) lz_scratch, Tensor(f!)? lengths, "
+                                "Tensor(g!)? ll_lengths, Tensor(h!)? d_lengths) -> ()", _png_deflate_lz_pack_impl)
+
+
+def png_deflate_lz_pack(filtered: torch.Tensor, adler_rows: torch.Tensor, stripe_rows: int, header: torch.Tensor, scratch: torch.Tensor,
+                        out: torch.Tensor, offsets: torch.Tensor, needed: torch.Tensor, lz_scratch: torch.Tensor,
+                        lengths: Optional[torch.Tensor] = None, ll_lengths: Optional[torch.Tensor] = None,
+                        d_lengths: Optional[torch.Tensor] = None):
+    """``png_deflate_pack`` with LZ77 matches (``torch.ops.sdv.k_png_deflate_lz_pack`` -> sdv_png_deflate_lz_pack; the stream rule is in
+    sdv_hip.h "Matching mode").  ``lz_scratch`` (``png_lz_scratch_bytes``) holds the tokens afterwards: as int32, the first n H R
+    words are the tokens (a stripe's from the index of its first filtered byte), the next n * stripes the token counts.  ``lengths``
+    receives the literal prices, ``ll_lengths`` [n, stripes, 286] / ``d_lengths`` [n, stripes, 30] the final code lengths."""
+    _k_png_deflate_lz_pack(filtered, adler_rows, int(stripe_rows), header, scratch, out, offsets, needed, lz_scratch, lengths, ll_lengths, d_lengths)
+
+
+def _png_crc32_impl(out, offsets, needed, acc):
+    if out.dtype != torch.uint8 or out.ndim != 1 or not out.is_contiguous():
+        raise SdvHipError(f"png_crc32: out must be a contiguous 1-D uint8 tensor, got {out.dtype} {tuple(out.shape)}")
+    if offsets.dtype != torch.int64 or offsets.ndim != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+        raise SdvHipError(f"png_crc32: offsets must be a contiguous int64 vector of n + 1 >= 2 elements, got {offsets.dtype} {tuple(offsets.shape)}")
+    n = offsets.numel() - 1
+    if needed.dtype != torch.int64 or needed.numel() != 1:
+        raise SdvHipError(f"png_crc32: needed must be one int64 element, got {needed.dtype} x {needed.numel()}")
+    if acc.dtype != torch.int32 or acc.numel() != n or not acc.is_contiguous():
+        raise SdvHipError(f"png_crc32: acc must be a contiguous int32 vector of n = {n} elements, got {acc.dtype} x {acc.numel()}")
+    lib = load()
+    args = (_ptr(out, name="out"), out.numel(), _ptr(offsets, name="offsets"), _ptr(needed, name="needed"), n, _ptr(acc, name="acc"))
+    _launch("png_crc32", dict(bytes=1.0 * out.numel()), lambda: _check(lib.sdv_png_crc32(*args, _stream()), "sdv_png_crc32"))
+
+
+_k_png_crc32 = _defop("k_png_crc32(Tensor(a!) out, Tensor offsets, Tensor needed, Tensor(b!) acc) -> ()", _png_crc32_impl)
+
+
+def png_crc32(out: torch.Tensor, offsets: torch.Tensor, needed: torch.Tensor, acc: torch.Tensor):
+    """Fill the IDAT CRC-32 of every file a packer left in ``out`` (``torch.ops.sdv.k_png_crc32`` -> sdv_png_crc32), in place; nothing
+    happens when ``needed`` exceeds ``out.numel()``.  ``acc``: int32 [n] workspace."""
+    _k_png_crc32(out, offsets, needed, acc)

@@ -118,6 +118,7 @@ class StableDiffusionWalkPipeline:
         self.upsampler = None
         self.jpeg_quality = 75             # output_type="jpeg" and .jpg / .jpeg frame files (what PIL's Image.save writes for them)
         self.png_encoder = "pil"           # .png frame files: "pil" = Image.save on the host, "hip" = compressed in HBM (png.py); SDV_PNG wins
+        self.png_matches = False           # the HIP PNG encoder's LZ77 matches and GPU-side CRC-32 (smaller files, more kernel time); SDV_PNG_MATCHES wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
@@ -577,7 +578,7 @@ class StableDiffusionWalkPipeline:
             image = encoder_for(self.jpeg_quality, u8.device).encode(u8[:B_real])
         elif output_type == "png":
             from .png import encoder_for
-            image = encoder_for(u8.device).encode(u8[:B_real])
+            image = encoder_for(u8.device, matches=self.png_matches_choice()).encode(u8[:B_real])
         elif want_float:
             image = f32[:B_real].cpu().numpy()                                                    # :438
         else:
@@ -630,6 +631,16 @@ class StableDiffusionWalkPipeline:
         if choice not in ("pil", "hip"):
             raise ValueError(f"SDV_PNG / png_encoder must be 'pil' or 'hip', got {choice!r}")
         return choice
+
+    def png_matches_choice(self) -> bool:
+        """Whether the HIP PNG encoder looks for matches: the environment variable SDV_PNG_MATCHES (``1`` / ``0``) when it is set, else
+        ``self.png_matches``."""
+        env = os.environ.get("SDV_PNG_MATCHES")
+        if env is None or env == "":
+            return bool(self.png_matches)
+        if env not in ("0", "1"):
+            raise ValueError(f"SDV_PNG_MATCHES must be '1' or '0', got {env!r}")
+        return env == "1"
 
     def make_clip_frames(self, prompt_a: str, prompt_b: str, seed_a: int, seed_b: int, num_interpolation_steps: int = 5,
                          save_path: Union[str, Path] = "outputs/", num_inference_steps: int = 50,
@@ -690,7 +701,7 @@ class StableDiffusionWalkPipeline:
                     encoder = encoder_for(self.jpeg_quality, outputs.device)
                 else:
                     from .png import encoder_for as png_encoder_for
-                    encoder = png_encoder_for(outputs.device)
+                    encoder = png_encoder_for(outputs.device, matches=self.png_matches_choice())
                 for data in encoder.encode(outputs):
                     writer.submit_bytes(data, save_path / (f"frame%06d{image_file_ext}" % indices[pos]))
                     pos += 1

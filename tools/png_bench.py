@@ -1,6 +1,6 @@
 """GPU PNG encoder (png.PngEncoder) against the host-side PIL encode it can replace, on the same box.
 
-    python tools/png_bench.py [--out FILE] [--reps 5] [--no-walk]
+    python tools/png_bench.py [--out FILE] [--reps 5] [--no-walk] [--matches]
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -9,6 +9,10 @@ in HBM, the copies back to pinned memory and the host CRC-32 included (encode() 
 the same call.  PIL: Image.fromarray(frame).save(buffer, "PNG") on FrameWriter's thread count - what the default path does after
 copying the raw frames to the host; per-core time is that of one thread.  Then a 60-frame walk() of the tiny pipeline at 512 x 512 with
 SDV_PNG=hip and without.  There is no fallback: without a GPU this tool fails.
+
+--matches: the same table with, per case, the four encoder modes (Huffman-only / matches x host CRC / GPU CRC) side by side: kernel
+launches per encode(), encode() time (HIP events and host clock), the deflate stage alone, file bytes per frame against PIL's; the
+walk is then run a third time with SDV_PNG_MATCHES=1.
 """
 from __future__ import annotations
 
@@ -110,8 +114,53 @@ def measure(name: str, dev_frames: torch.Tensor, threads: int, reps: int) -> dic
     return case
 
 
-def walk_rate(pipe, png: str, frames: int = 60) -> dict:
+def measure_modes(dev_frames: torch.Tensor, reps: int, pil_bytes: int) -> list:
+    """encode() in the four modes of PngEncoder on the same frames."""
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.png import PngEncoder
+    n = dev_frames.shape[0]
+    rows = []
+    for matches in (False, True):
+        for gpu_crc in (False, True):
+            enc = PngEncoder(dev_frames.device, matches=matches, gpu_crc=gpu_crc)
+            enc.encode(dev_frames)                                               # warm-up (and the retry, if any)
+            files = enc.encode(dev_frames)
+            gpu_ms, wall_ms, pack_ms = [], [], []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e0.record()
+                files = enc.encode(dev_frames)
+                e1.record()
+                e1.synchronize()
+                wall_ms.append((time.perf_counter() - t0) * 1e3)
+                gpu_ms.append(e0.elapsed_time(e1))
+            ws = next(iter(enc._ws.values()))
+            for _ in range(reps):                                                # deflate (+ CRC) launches alone
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                enc._pack(ws, n, False)
+                e1.record()
+                e1.synchronize()
+                pack_ms.append(e0.elapsed_time(e1))
+            med = lambda v: float(np.median(v))
+            size = int(sum(len(f) for f in files) // n)
+            rows.append(dict(matches=matches, gpu_crc=gpu_crc, kernel_launches=1 + (6 if matches else 3) + (2 if gpu_crc else 0),
+                             encode_ms_events=round(med(gpu_ms), 3), encode_ms_host_clock=round(med(wall_ms), 3),
+                             encode_ms_per_frame=round(med(wall_ms) / n, 4), deflate_crc_kernels_ms=round(med(pack_ms), 3),
+                             file_bytes_per_frame=size, file_bytes_vs_pil=round(size / pil_bytes, 3), retries=enc.retries,
+                             token_scratch_bytes=int(ws["lz_scratch"].numel()) if matches else 0))
+            del enc, ws
+            torch.cuda.empty_cache()
+    return rows
+
+
+def walk_rate(pipe, png: str, frames: int = 60, matches: bool = False) -> dict:
     os.environ["SDV_PNG"] = png
+    if matches:
+        os.environ["SDV_PNG_MATCHES"] = "1"
     rates = []
     try:
         for rep in range(2):                                                     # the first walk pays graph capture and workspaces
@@ -124,7 +173,8 @@ def walk_rate(pipe, png: str, frames: int = 60) -> dict:
                 size = sum(f.stat().st_size for f in Path(tmp).rglob("*.png")) // frames
     finally:
         del os.environ["SDV_PNG"]
-    case = dict(walk_frames=frames, SDV_PNG=png, frames_per_sec=round(rates[-1], 2), first_walk_frames_per_sec=round(rates[0], 2),
+        os.environ.pop("SDV_PNG_MATCHES", None)
+    case = dict(walk_frames=frames, SDV_PNG=png, SDV_PNG_MATCHES=int(matches), frames_per_sec=round(rates[-1], 2), first_walk_frames_per_sec=round(rates[0], 2),
                 file_bytes_per_frame=int(size))
     print(json.dumps(case), flush=True)
     return case
@@ -135,6 +185,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-walk", action="store_true")
+    ap.add_argument("--matches", action="store_true", help="also measure the matching mode and the GPU-side CRC-32")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("png_bench needs the GPU (no fallback)")
@@ -156,11 +207,17 @@ def main():
     for name, frames in (("tiny pipeline", small), ("uniform noise", torch.randint(0, 256, (128, 512, 512, 3), dtype=torch.uint8, generator=gen).to(dev)),
                          ("tiny pipeline x4 upsampler", big),
                          ("uniform noise", torch.randint(0, 256, (8, 2048, 2048, 3), dtype=torch.uint8, generator=gen).to(dev))):
-        result["cases"].append(measure(name, frames.contiguous(), threads, args.reps))
+        case = measure(name, frames.contiguous(), threads, args.reps)
+        if args.matches:
+            case["modes"] = measure_modes(frames.contiguous(), args.reps, case["file_bytes_per_frame_pil"])
+            print(json.dumps(case["modes"]), flush=True)
+        result["cases"].append(case)
     del small, big, up
     if not args.no_walk:
         for png in ("pil", "hip"):
             result["walks"].append(walk_rate(pipe, png))
+        if args.matches:
+            result["walks"].append(walk_rate(pipe, "hip", matches=True))
     line = json.dumps(result)
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
