@@ -270,6 +270,7 @@ int sdv_groupnorm_finalize(const float* P1, int32_t C1, int32_t ld1, int32_t bpi
                            int32_t nimg, int32_t groups, int32_t splits, float* partials, void* stream);
 int sdv_groupnorm_stats(const sdv_bf16* X, const sdv_bf16* X2, int32_t C1, int32_t C2, int32_t nimg,
                         int32_t HW, int32_t groups, int32_t splits, float* partials, void* stream);
+/* Like sdv_groupnorm_stats, apply (bf16 and fp8) refuses splits <= 0, nimg <= 0 and HW <= 0 before any launch. */
 int sdv_groupnorm_apply(const sdv_bf16* X, const sdv_bf16* X2, int32_t C1, int32_t C2, int32_t nimg,
                         int32_t HW, int32_t groups, int32_t splits, const float* partials,
                         const float* gamma, const float* beta, float eps, int32_t silu, sdv_bf16* Y,

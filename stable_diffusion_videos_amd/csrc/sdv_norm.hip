@@ -441,6 +441,7 @@ static int gn_apply_launch(const sdv_bf16* X, const sdv_bf16* X2, int32_t C1, in
     const int C = C1 + C2;
     SDV_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0 && C > 0, "sdv_groupnorm_apply: channels must be multiples of 8");
     SDV_REQUIRE(groups > 0 && groups <= 64 && C % groups == 0, "sdv_groupnorm_apply: bad groups");
+    SDV_REQUIRE(splits > 0 && nimg > 0 && HW > 0, "sdv_groupnorm_apply: bad sizes");
     // Elements per block: ~4k blocks in total, between 16 K and 128 K elements each.  Measured at 128 samples
     // (tools/gn_bench.py): 64^2 x 320 channels 3.4 TB/s with 16 K-element blocks (10 k blocks) vs 5.0 TB/s with 64 K; the
     // 32^2 / 16^2 levels are best at 16 K - 32 K.
