@@ -503,6 +503,58 @@ int sdv_png_deflate_lz_pack(const uint8_t* filtered, const uint32_t* adler_rows,
                             int64_t lz_scratch_bytes, uint8_t* ll_lengths, uint8_t* d_lengths, void* stream);
 int sdv_png_crc32(uint8_t* out, int64_t out_cap, const int64_t* offsets, const int64_t* needed, int32_t n, uint32_t* acc, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * H.264 CAVLC intra encoder (utils.py:69-128: the reference's libx264 crf 10 yuv420p track).  Four additive entry points (50 with
+ * them; the ABI version stays 12); opt-in (video.py: SDV_VIDEO_CODEC=h264-cavlc), the default track is untouched.
+ *
+ * Stream rule.  Parameter sets: those of the I_PCM track (profile 66 with constraint_set0/1, CAVLC, POC type 2, deblocking control
+ * present, pic_init_qp 26).  Per picture one IDR slice NAL unit per macroblock row: first_mb_in_slice = row * mbw, slice_type 7,
+ * frame_num 0, idr_pic_id = (first_index + frame) & 1 in every slice of the picture, slice_qp_delta = qp - 26,
+ * disable_deblocking_filter_idc 1.  A slice boundary makes the row above unavailable: every row is an independent byte-aligned bit
+ * stream, and one mp4 sample is the picture's mbh slices, each behind its 4-byte big-endian length.
+ *   Macroblocks: Intra16x16, prediction mode 2 (DC: 128 for the first macroblock of a row, else (sum of the 16 reconstructed samples
+ *   left of it + 8) >> 4), intra_chroma_pred_mode 0 (DC, 8.3.4 with the left neighbour only: per half column (sum of 4 + 2) >> 2),
+ *   mb_qp_delta 0, mb_type = 1 + 2 + 4 cbp_chroma + 12 (cbp_luma == 15); cbp_luma = 15 when any luma AC level is nonzero, else 0;
+ *   cbp_chroma = 2 when any chroma AC level is nonzero, else 1 when any chroma DC level is, else 0.
+ *   Transform: W = Cf X Cf^T per 4x4 block of source - prediction; luma DCs Yd = (H Wd H + 1) >> 1, chroma DCs Yd = H2 Wd H2.
+ *   Quantisation: |Z| = (|W| MF + f) >> qbits, sign kept, qbits = 15 + qp / 6, f = (1 << qbits) / 3, MF by qp % 6 and position class
+ *   {13107 5243 8066, 11916 4660 7490, 10082 4194 6554, 9362 3647 5825, 8192 3355 5243, 7282 2893 4559}; DC blocks 2 f and
+ *   qbits + 1.  Chroma uses QPc of Table 8-15 (chroma_qp_index_offset 0).
+ *   CAVLC (9.2): Intra16x16DCLevel, the 16 AC blocks by luma4x4BlkIdx (15 levels each; only with cbp_luma 15), chroma DC Cb / Cr (with
+ *   cbp_chroma > 0), chroma AC Cb 0..3, Cr 0..3 (with cbp_chroma 2).  nC from the AC TotalCoeff of the left / top blocks, the row above
+ *   unavailable, an I_PCM neighbour counting 16.
+ *   Reconstruction per 8.5 (dequantise, inverse transforms, clip) feeds the next macroblock's prediction.
+ *   I_PCM (mb_type 25, alignment zeros, the 384 source samples) when macroblock_layer() would take more than 3200 bits (A.3.1) or a
+ *   level needs level_prefix > 15; its reconstruction is the source, its blocks count TotalCoeff 16.
+ *   Colour: Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16, Cb = ((S(-38 R - 74 G + 112 B) + 512) >> 10) + 128,
+ *   Cr = ((S(112 R - 94 G - 18 B) + 512) >> 10) + 128, S the sum over the 2 x 2 box; planes edge-replicated to multiples of 16.
+ *   NAL header 0x65 and emulation prevention as in h264.nal_unit.
+ *
+ * Capacity.  A macroblock takes at most 3200 bits = 400 bytes (I_PCM: 9 + 7 + 3072 bits), the slice header and the stop bit at most
+ * 8 bytes, so a slice's RBSP at most 400 mbw + 8 bytes; emulation prevention adds at most one byte per two; with the NAL header and
+ * the 4-byte length one slice takes at most
+ *     slot = 5 + (400 mbw + 8) + (400 mbw + 8) / 2 = 600 mbw + 17 bytes,
+ * a batch at most n mbh slot bytes - the out_cap that the packer demands (less is refused, nothing is launched).  The scratch buffer
+ * holds one slot per slice at a stride of slot rounded up to 8, then an int64 start and an int32 length per slice:
+ *     scratch_bytes >= n mbh (((slot + 7) & ~7) + 12).
+ *
+ * sdv_h264_planes_u8      frames uint8 [n][H][W][3] (H, W even, 2 .. 16384) -> y uint8 [n][16 mbh][16 mbw], cb / cr uint8
+ *   [n][8 mbh][8 mbw].  One launch.
+ * sdv_h264_encode_rows    planes (y 16-byte, cb / cr 8-byte aligned) -> every slice complete in its slot of scratch (8-byte aligned),
+ *   and its length.  qp 0 .. 51.  One launch, one wave per slice.
+ * sdv_h264_pack           slots -> out, the slices back to back in sample order; offsets int64 [n + 1]: sample k is
+ *   out[offsets[k] .. offsets[k + 1]).  Two launches (scan, copy).
+ * sdv_h264_vlc_tables     HOST pointers, no GPU work: the kernel's VLC tables as lengths uint8 [656] and codes uint16 [656] (length 0 =
+ *   no such symbol).  coeff_token at [68 t + 4 TotalCoeff + TrailingOnes] for the tables t of nC 0-1, 2-3, 4-7, 8+, chroma DC at
+ *   [272 + 4 TotalCoeff + TrailingOnes]; total_zeros at [292 + 16 (TotalCoeff - 1) + total_zeros], chroma DC at
+ *   [532 + 4 (TotalCoeff - 1) + total_zeros]; run_before at [544 + 16 (min(zerosLeft, 7) - 1) + run_before]. */
+int sdv_h264_planes_u8(const uint8_t* frames, int32_t n, int32_t H, int32_t W, uint8_t* y, uint8_t* cb, uint8_t* cr, void* stream);
+int sdv_h264_encode_rows(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, int32_t n, int32_t mbh, int32_t mbw, int32_t qp,
+                         int32_t first_index, void* scratch, int64_t scratch_bytes, void* stream);
+int sdv_h264_pack(void* scratch, int64_t scratch_bytes, int32_t n, int32_t mbh, int32_t mbw, uint8_t* out, int64_t out_cap,
+                  int64_t* offsets, void* stream);
+int sdv_h264_vlc_tables(uint8_t* host_lengths, uint16_t* host_codes, int32_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,211 @@
+// H.264 CAVLC intra encoder (sdv_hip.h "H.264 CAVLC intra encoder"): uint8 RGB frames in HBM -> mp4 samples in one packed buffer.
+//
+//   sdv_h264_planes_u8     frames -> Y / Cb / Cr planes, integer BT.601, edge-replicated to whole macroblocks
+//   sdv_h264_encode_rows   planes -> one complete slice (4-byte length | NAL header | payload with emulation prevention) per macroblock
+//                          row and frame, each in its own slot of the scratch buffer, plus its length
+//   sdv_h264_pack          slots -> one contiguous buffer in sample order, and offsets[n + 1]
+//   sdv_h264_vlc_tables    host only: the VLC tables of the kernel as (length, code) pairs
+//
+// Stream: one IDR slice per macroblock row, so the n * mbh rows are independent bit streams; inside a row every macroblock predicts from
+// the reconstruction of the one before it - a serial chain.  One workgroup = one wave = one row: all lanes stage the macroblock's 384
+// samples in LDS with 16- and 8-byte loads, lane 0 walks the chain (sdv_h264_core.h: transform, quantisation, CAVLC, the I_PCM decision,
+// reconstruction of the right columns) with the levels in LDS.  The chains of a batch (4096 at 128 frames of 512 x 512) fill the GPU's
+// wave slots; the work inside a chain is not spread over the lanes.
+#include "sdv_common.h"
+#include "sdv_h264_core.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+
+SDV_DEVICE int h264_luma(int r, int g, int b) { return ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16; }
+
+// One thread per 2 x 2 samples of the padded planes.  Luma reads the pixel clamped into the frame; chroma reads the 2 x 2 box of the
+// chroma position clamped into the frame's chroma grid - which is the edge replication of the finished planes.
+__global__ __launch_bounds__(kThreads) void h264_planes_kernel(const uint8_t* __restrict__ frames, int H, int W, int ph, int pw,
+                                                               uint8_t* __restrict__ y, uint8_t* __restrict__ cb, uint8_t* __restrict__ cr) {
+    const int cw = pw / 2, chh = ph / 2;
+    const int cx = blockIdx.x * kThreads + threadIdx.x, cy = blockIdx.y;
+    const long long f = blockIdx.z;
+    if (cx >= cw) return;
+    const uint8_t* img = frames + f * H * W * 3;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const int py = 2 * cy + (d >> 1), px = 2 * cx + (d & 1);
+        const uint8_t* p = img + ((long long)min(py, H - 1) * W + min(px, W - 1)) * 3;
+        y[(f * ph + py) * pw + px] = (uint8_t)h264_luma(p[0], p[1], p[2]);
+    }
+    const int sy = min(cy, H / 2 - 1), sx = min(cx, W / 2 - 1);
+    int rs = 0, gs = 0, bs = 0;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const uint8_t* p = img + ((long long)(2 * sy + (d >> 1)) * W + 2 * sx + (d & 1)) * 3;
+        rs += p[0], gs += p[1], bs += p[2];
+    }
+    cb[(f * chh + cy) * cw + cx] = (uint8_t)(((-38 * rs - 74 * gs + 112 * bs + 512) >> 10) + 128);
+    cr[(f * chh + cy) * cw + cx] = (uint8_t)(((112 * rs - 94 * gs - 18 * bs + 512) >> 10) + 128);
+}
+
+__global__ __launch_bounds__(64) void h264_rows_kernel(const uint8_t* __restrict__ y, const uint8_t* __restrict__ cb, const uint8_t* __restrict__ cr,
+                                                       int mbh, int mbw, int qp, int first_index, uint8_t* __restrict__ slots, long long stride,
+                                                       long long slot_bytes, int32_t* __restrict__ lens) {
+    __shared__ __attribute__((aligned(16))) uint8_t sy[256];
+    __shared__ __attribute__((aligned(16))) uint8_t sc[128];
+    __shared__ int16_t lev[kH264MbLevels];
+    const int lane = threadIdx.x;
+    const long long row = blockIdx.x;
+    const int r = (int)(row % mbh);
+    const long long f = row / mbh;
+    uint8_t* slot = slots + row * stride;
+    h264_writer w;
+    h264_chain ch;
+    w.init(slot + 5, slot_bytes - 5);
+    ch.have = 0;
+    if (lane == 0) h264_slice_header(w, (unsigned)(r * mbw), (unsigned)((first_index + f) & 1), qp);
+    const uint8_t* yrow = y + (f * mbh + r) * 16 * ((long long)mbw * 16);
+    const long long crow = (f * mbh + r) * 8 * ((long long)mbw * 8);
+    for (int m = 0; m < mbw; ++m) {
+        if (lane < 16) {
+            *(uint4*)(sy + lane * 16) = *(const uint4*)(yrow + (long long)lane * (mbw * 16) + m * 16);
+        } else if (lane < 32) {
+            const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+            *(uint2*)(sc + c * 64 + i * 8) = *(const uint2*)((c ? cr : cb) + crow + (long long)i * (mbw * 8) + m * 8);
+        }
+        __syncthreads();
+        if (lane == 0) h264_encode_mb(sy, sc, lev, ch, qp, w);
+        __syncthreads();
+    }
+    if (lane == 0) {
+        w.put(1u, 1);                                   // rbsp_slice_trailing_bits
+        while (w.n) w.put(0u, 1);
+        const long long used = min(w.pos, slot_bytes - 5);      // (the capacity bound keeps pos below it; nothing was stored beyond)
+        const unsigned len = (unsigned)(1 + used);
+        slot[0] = (uint8_t)(len >> 24), slot[1] = (uint8_t)(len >> 16), slot[2] = (uint8_t)(len >> 8), slot[3] = (uint8_t)len;
+        slot[4] = 0x65;                                 // nal_ref_idc 3, nal_unit_type 5
+        lens[row] = (int32_t)(5 + used);
+    }
+}
+
+// ONE workgroup: exclusive scan of the slice lengths, frame-major -> starts[row], offsets[frame], offsets[n]
+__global__ __launch_bounds__(kThreads) void h264_scan_kernel(const int32_t* __restrict__ lens, long long* __restrict__ starts, long long rows, int mbh,
+                                                             long long* __restrict__ offsets) {
+    __shared__ long long wsum[kThreads / 64];
+    __shared__ long long running;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) running = 0;
+    __syncthreads();
+    for (long long i0 = 0; i0 < rows; i0 += kThreads) {
+        const long long i = i0 + tid;
+        const long long mine = i < rows ? (long long)lens[i] : 0;
+        long long incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        long long before = running;
+        for (int k = 0; k < wave; ++k) before += wsum[k];
+        if (i < rows) {
+            starts[i] = before + incl - mine;
+            if (i % mbh == 0) offsets[i / mbh] = before + incl - mine;
+        }
+        __syncthreads();
+        if (tid == kThreads - 1) running = before + incl;
+        __syncthreads();
+    }
+    if (tid == 0) offsets[rows / mbh] = running;
+}
+
+__global__ __launch_bounds__(kThreads) void h264_copy_kernel(const uint8_t* __restrict__ slots, long long stride, const int32_t* __restrict__ lens,
+                                                             const long long* __restrict__ starts, uint8_t* __restrict__ out, long long out_cap) {
+    const long long row = blockIdx.x;
+    const uint8_t* src = slots + row * stride;
+    const long long at = starts[row];
+    const int len = lens[row];
+    for (int i = threadIdx.x; i < len; i += kThreads)
+        if (at + i < out_cap) out[at + i] = src[i];
+}
+
+struct h264_layout {
+    long long rows, slot, stride, starts_at, lens_at, bytes;
+};
+h264_layout h264_scratch_layout(int n, int mbh, int mbw) {
+    h264_layout l;
+    l.rows = (long long)n * mbh;
+    l.slot = 600LL * mbw + 17;                          // the capacity formula of sdv_hip.h
+    l.stride = (l.slot + 7) & ~7LL;
+    l.starts_at = l.rows * l.stride;
+    l.lens_at = l.starts_at + 8 * l.rows;
+    l.bytes = l.lens_at + 4 * l.rows;
+    return l;
+}
+
+}  // namespace
+
+#define H264_GRID_ARGS(name)                                                                                                       \
+    SDV_REQUIRE(n > 0 && n <= 65535, name ": bad frame count n=%d (1 .. 65535)", n);                                                \
+    SDV_REQUIRE(mbh >= 1 && mbh <= 1024 && mbw >= 1 && mbw <= 1024, name ": bad macroblock grid mbh=%d mbw=%d (1 .. 1024)", mbh, mbw); \
+    SDV_REQUIRE((long long)n * mbh < 0x7fffffffLL, name ": too many macroblock rows for one grid")
+
+extern "C" int sdv_h264_planes_u8(const uint8_t* frames, int32_t n, int32_t H, int32_t W, uint8_t* y, uint8_t* cb, uint8_t* cr, void* stream) {
+    SDV_REQUIRE(frames && y && cb && cr, "sdv_h264_planes_u8: null pointer");
+    SDV_REQUIRE(n > 0 && n <= 65535, "sdv_h264_planes_u8: bad frame count n=%d (1 .. 65535)", n);
+    SDV_REQUIRE(H >= 2 && H <= 16384 && W >= 2 && W <= 16384 && H % 2 == 0 && W % 2 == 0,
+                "sdv_h264_planes_u8: bad frame size H=%d W=%d (even, 2 .. 16384)", H, W);
+    const int ph = (H + 15) / 16 * 16, pw = (W + 15) / 16 * 16;
+    hipLaunchKernelGGL(h264_planes_kernel, dim3((unsigned)((pw / 2 + kThreads - 1) / kThreads), (unsigned)(ph / 2), (unsigned)n), dim3(kThreads), 0,
+                       (hipStream_t)stream, frames, H, W, ph, pw, y, cb, cr);
+    SDV_CHECK_LAUNCH("sdv_h264_planes_u8");
+    return SDV_OK;
+}
+
+extern "C" int sdv_h264_encode_rows(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, int32_t n, int32_t mbh, int32_t mbw, int32_t qp,
+                                    int32_t first_index, void* scratch, int64_t scratch_bytes, void* stream) {
+    SDV_REQUIRE(y && cb && cr && scratch, "sdv_h264_encode_rows: null pointer");
+    H264_GRID_ARGS("sdv_h264_encode_rows");
+    SDV_REQUIRE(qp >= 0 && qp <= 51, "sdv_h264_encode_rows: qp=%d outside 0 .. 51", qp);
+    SDV_REQUIRE(first_index >= 0, "sdv_h264_encode_rows: negative first_index");
+    const h264_layout l = h264_scratch_layout(n, mbh, mbw);
+    SDV_REQUIRE(scratch_bytes >= l.bytes, "sdv_h264_encode_rows: scratch buffer too small: %lld bytes, %lld slices of %d macroblocks need %lld",
+                (long long)scratch_bytes, l.rows, mbw, l.bytes);
+    SDV_REQUIRE((((uintptr_t)y) & 15) == 0 && (((uintptr_t)cb) & 7) == 0 && (((uintptr_t)cr) & 7) == 0 && (((uintptr_t)scratch) & 7) == 0,
+                "sdv_h264_encode_rows: y must be 16-byte, cb / cr / scratch 8-byte aligned");
+    uint8_t* base = (uint8_t*)scratch;
+    hipLaunchKernelGGL(h264_rows_kernel, dim3((unsigned)l.rows), dim3(64), 0, (hipStream_t)stream, y, cb, cr, mbh, mbw, qp, first_index, base, l.stride,
+                       l.slot, (int32_t*)(base + l.lens_at));
+    SDV_CHECK_LAUNCH("sdv_h264_encode_rows");
+    return SDV_OK;
+}
+
+extern "C" int sdv_h264_pack(void* scratch, int64_t scratch_bytes, int32_t n, int32_t mbh, int32_t mbw, uint8_t* out, int64_t out_cap,
+                             int64_t* offsets, void* stream) {
+    SDV_REQUIRE(scratch && out && offsets, "sdv_h264_pack: null pointer");
+    H264_GRID_ARGS("sdv_h264_pack");
+    const h264_layout l = h264_scratch_layout(n, mbh, mbw);
+    SDV_REQUIRE(scratch_bytes >= l.bytes, "sdv_h264_pack: scratch buffer too small: %lld bytes, %lld slices of %d macroblocks need %lld",
+                (long long)scratch_bytes, l.rows, mbw, l.bytes);
+    SDV_REQUIRE(out_cap >= l.rows * l.slot, "sdv_h264_pack: output capacity %lld below the bound %lld (%lld slices of at most %lld bytes)",
+                (long long)out_cap, l.rows * l.slot, l.rows, l.slot);
+    SDV_REQUIRE((((uintptr_t)scratch) & 7) == 0 && (((uintptr_t)offsets) & 7) == 0, "sdv_h264_pack: scratch / offsets must be 8-byte aligned");
+    uint8_t* base = (uint8_t*)scratch;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(h264_scan_kernel, dim3(1), dim3(kThreads), 0, s, (const int32_t*)(base + l.lens_at), (long long*)(base + l.starts_at), l.rows, mbh,
+                       (long long*)offsets);
+    SDV_CHECK_LAUNCH("sdv_h264_pack (scan)");
+    hipLaunchKernelGGL(h264_copy_kernel, dim3((unsigned)l.rows), dim3(kThreads), 0, s, (const uint8_t*)base, l.stride, (const int32_t*)(base + l.lens_at),
+                       (const long long*)(base + l.starts_at), out, (long long)out_cap);
+    SDV_CHECK_LAUNCH("sdv_h264_pack (copy)");
+    return SDV_OK;
+}
+
+extern "C" int sdv_h264_vlc_tables(uint8_t* lengths, uint16_t* codes, int32_t count) {
+    SDV_REQUIRE(lengths && codes, "sdv_h264_vlc_tables: null pointer");
+    SDV_REQUIRE(count == kH264VlcWords, "sdv_h264_vlc_tables: the tables hold %d words, got room for %d", (int)kH264VlcWords, count);
+    for (int i = 0; i < kH264VlcWords; ++i) {
+        lengths[i] = (uint8_t)(kH264VlcHost[i] >> 8);
+        codes[i] = (uint16_t)(kH264VlcHost[i] & 0xffu);
+    }
+    return SDV_OK;
+}

@@ -1,0 +1,406 @@
+// H.264 CAVLC intra encoder, the part that is plain C++ (sdv_hip.h "H.264 CAVLC intra encoder"): VLC tables, bit writer with emulation
+// prevention, transforms, quantisation, residual_block_cavlc(), and the macroblock step of a slice's chain.  Host and device compile the
+// same functions: the kernel in sdv_h264.hip walks a slice with them, the host-only table entry point reads the same words.
+#pragma once
+#include <stdint.h>
+
+// Tables 9-5, 9-7, 9-8, 9-9, 9-10 as (length << 8 | code) words; length 0 = no such symbol.
+#define SDV_H264_VLC_WORDS \
+    0x0101, 0x0000, 0x0000, 0x0000, 0x0605, 0x0201, 0x0000, 0x0000, 0x0807, 0x0604, 0x0301, 0x0000, 0x0907, 0x0806, 0x0705, 0x0503, \
+    0x0a07, 0x0906, 0x0805, 0x0603, 0x0b07, 0x0a06, 0x0905, 0x0704, 0x0d0f, 0x0b06, 0x0a05, 0x0804, 0x0d0b, 0x0d0e, 0x0b05, 0x0904, \
+    0x0d08, 0x0d0a, 0x0d0d, 0x0a04, 0x0e0f, 0x0e0e, 0x0d09, 0x0b04, 0x0e0b, 0x0e0a, 0x0e0d, 0x0d0c, 0x0f0f, 0x0f0e, 0x0e09, 0x0e0c, \
+    0x0f0b, 0x0f0a, 0x0f0d, 0x0e08, 0x100f, 0x0f01, 0x0f09, 0x0f0c, 0x100b, 0x100e, 0x100d, 0x0f08, 0x1007, 0x100a, 0x1009, 0x100c, \
+    0x1004, 0x1006, 0x1005, 0x1008, 0x0203, 0x0000, 0x0000, 0x0000, 0x060b, 0x0202, 0x0000, 0x0000, 0x0607, 0x0507, 0x0303, 0x0000, \
+    0x0707, 0x060a, 0x0609, 0x0405, 0x0807, 0x0606, 0x0605, 0x0404, 0x0804, 0x0706, 0x0705, 0x0506, 0x0907, 0x0806, 0x0805, 0x0608, \
+    0x0b0f, 0x0906, 0x0905, 0x0604, 0x0b0b, 0x0b0e, 0x0b0d, 0x0704, 0x0c0f, 0x0b0a, 0x0b09, 0x0904, 0x0c0b, 0x0c0e, 0x0c0d, 0x0b0c, \
+    0x0c08, 0x0c0a, 0x0c09, 0x0b08, 0x0d0f, 0x0d0e, 0x0d0d, 0x0c0c, 0x0d0b, 0x0d0a, 0x0d09, 0x0d0c, 0x0d07, 0x0e0b, 0x0d06, 0x0d08, \
+    0x0e09, 0x0e08, 0x0e0a, 0x0d01, 0x0e07, 0x0e06, 0x0e05, 0x0e04, 0x040f, 0x0000, 0x0000, 0x0000, 0x060f, 0x040e, 0x0000, 0x0000, \
+    0x060b, 0x050f, 0x040d, 0x0000, 0x0608, 0x050c, 0x050e, 0x040c, 0x070f, 0x050a, 0x050b, 0x040b, 0x070b, 0x0508, 0x0509, 0x040a, \
+    0x0709, 0x060e, 0x060d, 0x0409, 0x0708, 0x060a, 0x0609, 0x0408, 0x080f, 0x070e, 0x070d, 0x050d, 0x080b, 0x080e, 0x070a, 0x060c, \
+    0x090f, 0x080a, 0x080d, 0x070c, 0x090b, 0x090e, 0x0809, 0x080c, 0x0908, 0x090a, 0x090d, 0x0808, 0x0a0d, 0x0907, 0x0909, 0x090c, \
+    0x0a09, 0x0a0c, 0x0a0b, 0x0a0a, 0x0a05, 0x0a08, 0x0a07, 0x0a06, 0x0a01, 0x0a04, 0x0a03, 0x0a02, 0x0603, 0x0000, 0x0000, 0x0000, \
+    0x0600, 0x0601, 0x0000, 0x0000, 0x0604, 0x0605, 0x0606, 0x0000, 0x0608, 0x0609, 0x060a, 0x060b, 0x060c, 0x060d, 0x060e, 0x060f, \
+    0x0610, 0x0611, 0x0612, 0x0613, 0x0614, 0x0615, 0x0616, 0x0617, 0x0618, 0x0619, 0x061a, 0x061b, 0x061c, 0x061d, 0x061e, 0x061f, \
+    0x0620, 0x0621, 0x0622, 0x0623, 0x0624, 0x0625, 0x0626, 0x0627, 0x0628, 0x0629, 0x062a, 0x062b, 0x062c, 0x062d, 0x062e, 0x062f, \
+    0x0630, 0x0631, 0x0632, 0x0633, 0x0634, 0x0635, 0x0636, 0x0637, 0x0638, 0x0639, 0x063a, 0x063b, 0x063c, 0x063d, 0x063e, 0x063f, \
+    0x0201, 0x0000, 0x0000, 0x0000, 0x0607, 0x0101, 0x0000, 0x0000, 0x0604, 0x0606, 0x0301, 0x0000, 0x0603, 0x0703, 0x0702, 0x0605, \
+    0x0602, 0x0803, 0x0802, 0x0700, 0x0101, 0x0303, 0x0302, 0x0403, 0x0402, 0x0503, 0x0502, 0x0603, 0x0602, 0x0703, 0x0702, 0x0803, \
+    0x0802, 0x0903, 0x0902, 0x0901, 0x0307, 0x0306, 0x0305, 0x0304, 0x0303, 0x0405, 0x0404, 0x0403, 0x0402, 0x0503, 0x0502, 0x0603, \
+    0x0602, 0x0601, 0x0600, 0x0000, 0x0405, 0x0307, 0x0306, 0x0305, 0x0404, 0x0403, 0x0304, 0x0303, 0x0402, 0x0503, 0x0502, 0x0601, \
+    0x0501, 0x0600, 0x0000, 0x0000, 0x0503, 0x0307, 0x0405, 0x0404, 0x0306, 0x0305, 0x0304, 0x0403, 0x0303, 0x0402, 0x0502, 0x0501, \
+    0x0500, 0x0000, 0x0000, 0x0000, 0x0405, 0x0404, 0x0403, 0x0307, 0x0306, 0x0305, 0x0304, 0x0303, 0x0402, 0x0501, 0x0401, 0x0500, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0601, 0x0501, 0x0307, 0x0306, 0x0305, 0x0304, 0x0303, 0x0302, 0x0401, 0x0301, 0x0600, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0601, 0x0501, 0x0305, 0x0304, 0x0303, 0x0203, 0x0302, 0x0401, 0x0301, 0x0600, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0601, 0x0401, 0x0501, 0x0303, 0x0203, 0x0202, 0x0302, 0x0301, 0x0600, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0601, 0x0600, 0x0401, 0x0203, 0x0202, 0x0301, 0x0201, 0x0501, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0501, 0x0500, 0x0301, 0x0203, 0x0202, 0x0201, 0x0401, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0400, 0x0401, 0x0301, 0x0302, 0x0101, 0x0303, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0400, 0x0401, 0x0201, 0x0101, 0x0301, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0300, 0x0301, 0x0101, 0x0201, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0200, 0x0201, 0x0101, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0100, 0x0101, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0000, 0x0000, 0x0000, 0x0000, 0x0101, 0x0201, 0x0301, 0x0300, 0x0101, 0x0201, 0x0200, 0x0000, 0x0101, 0x0100, 0x0000, 0x0000, \
+    0x0101, 0x0100, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0101, 0x0201, 0x0200, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0203, 0x0202, 0x0201, 0x0200, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0203, 0x0202, 0x0201, 0x0301, 0x0300, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0203, 0x0202, 0x0303, 0x0302, 0x0301, 0x0300, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0203, 0x0300, 0x0301, 0x0303, 0x0302, 0x0305, 0x0304, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, 0x0000, \
+    0x0307, 0x0306, 0x0305, 0x0304, 0x0303, 0x0302, 0x0301, 0x0401, 0x0501, 0x0601, 0x0701, 0x0801, 0x0901, 0x0a01, 0x0b01, 0x0000
+
+// Offsets into the table above.  coeff_token: [table][4 * TotalCoeff + TrailingOnes], tables nC 0-1 | 2-3 | 4-7 | 8+ (68 words each), then
+// chroma DC (20 words); total_zeros: [TotalCoeff - 1][total_zeros] (16 words a row), chroma DC (4 words a row); run_before:
+// [min(zerosLeft, 7) - 1][run_before] (16 words a row).
+enum { kH264CoeffToken = 0, kH264CoeffTokenChromaDc = 272, kH264TotalZeros = 292, kH264TotalZerosChromaDc = 532, kH264RunBefore = 544,
+       kH264VlcWords = 656 };
+
+static const uint16_t kH264VlcHost[kH264VlcWords] = {SDV_H264_VLC_WORDS};
+#ifdef __HIPCC__
+__constant__ const uint16_t kH264VlcDev[kH264VlcWords] = {SDV_H264_VLC_WORDS};
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SDV_H264_VLC kH264VlcDev
+#else
+#define SDV_H264_VLC kH264VlcHost
+#endif
+#ifdef __HIPCC__
+#define H264_HD __host__ __device__ inline
+#else
+#define H264_HD inline
+#endif
+
+// MF (forward quantiser) and normAdjust4x4 (8.5.9) by qp % 6 and position class: 0 = both indices even, 1 = both odd, 2 = mixed
+H264_HD int h264_mf(int q6, int cls) {
+    const int t[18] = {13107, 5243, 8066, 11916, 4660, 7490, 10082, 4194, 6554, 9362, 3647, 5825, 8192, 3355, 5243, 7282, 2893, 4559};
+    return t[q6 * 3 + cls];
+}
+H264_HD int h264_norm(int q6, int cls) {
+    const int t[18] = {10, 16, 13, 11, 18, 14, 13, 20, 16, 14, 23, 18, 16, 25, 20, 18, 29, 23};
+    return t[q6 * 3 + cls];
+}
+H264_HD int h264_pos_class(int i, int j) { return ((i | j) & 1) == 0 ? 0 : ((i & j) & 1) ? 1 : 2; }
+H264_HD int h264_qpc(int qp) {                          // Table 8-15, chroma_qp_index_offset 0
+    const uint8_t t[22] = {29, 30, 31, 32, 32, 33, 34, 34, 35, 35, 36, 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39};
+    return qp < 30 ? qp : t[qp - 30];
+}
+H264_HD int h264_zigzag(int k) {                        // raster index (row * 4 + column) of scan position k
+    const uint8_t t[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
+    return t[k];
+}
+H264_HD int h264_scan_pos(int r) {                      // the inverse: scan position of raster index r
+    const uint8_t t[16] = {0, 1, 5, 6, 2, 4, 7, 12, 3, 8, 11, 13, 9, 10, 14, 15};
+    return t[r];
+}
+
+// The slice's bit stream: MSB first, emulation prevention (7.4.1) applied as the bytes leave, never a store at or beyond cap.
+struct h264_writer {
+    uint8_t* out;
+    long long cap, pos;
+    unsigned long long acc;
+    int n, zeros;
+    long long bits;
+    bool failed;
+    H264_HD void init(uint8_t* o, long long c) { out = o, cap = c, pos = 0, acc = 0, n = 0, zeros = 0, bits = 0, failed = false; }
+    H264_HD void emit(unsigned b) {
+        if (zeros >= 2 && b <= 3u) {
+            if (pos < cap) out[pos] = 3;
+            ++pos;
+            zeros = 0;
+        }
+        if (pos < cap) out[pos] = (uint8_t)b;
+        ++pos;
+        zeros = b == 0u ? zeros + 1 : 0;
+    }
+    H264_HD void put(unsigned v, int len) {             // len <= 32
+        acc = (acc << len) | v;
+        n += len;
+        bits += len;
+        while (n >= 8) {
+            emit((unsigned)(acc >> (n - 8)) & 0xffu);
+            n -= 8;
+        }
+    }
+    H264_HD void fail() { failed = true; }
+};
+struct h264_counter {
+    long long bits;
+    bool failed;
+    H264_HD void put(unsigned, int len) { bits += len; }
+    H264_HD void fail() { failed = true; }
+};
+
+template <class Sink>
+H264_HD void h264_put_ue(Sink& s, unsigned v) {
+    int len = 0;
+    for (unsigned t = v + 1; t; t >>= 1) ++len;
+    s.put(v + 1, 2 * len - 1);
+}
+template <class Sink>
+H264_HD void h264_put_se(Sink& s, int v) { h264_put_ue(s, v > 0 ? (unsigned)(2 * v - 1) : (unsigned)(-2 * v)); }
+template <class Sink>
+H264_HD void h264_put_vlc(Sink& s, int index) {
+    const unsigned w = SDV_H264_VLC[index];
+    s.put(w & 0xffu, (int)(w >> 8));
+}
+
+// residual_block_cavlc() (7.3.5.3.2, 9.2) of maxc levels in scan order; returns TotalCoeff.  A level that needs level_prefix > 15 marks the
+// sink failed (the macroblock is then coded I_PCM).
+template <class Sink>
+H264_HD int h264_code_block(const int16_t* lv, int maxc, int nC, Sink& s) {
+    int idx[16];
+    int total = 0;
+    for (int i = 0; i < maxc; ++i)
+        if (lv[i]) idx[total++] = i;
+    int t1 = 0;
+    for (int k = total - 1; k >= 0 && t1 < 3; --k) {
+        const int v = lv[idx[k]];
+        if (v != 1 && v != -1) break;
+        ++t1;
+    }
+    const int table = nC < 0 ? 4 : nC < 2 ? 0 : nC < 4 ? 1 : nC < 8 ? 2 : 3;
+    h264_put_vlc(s, kH264CoeffToken + table * 68 + 4 * total + t1);
+    if (!total) return 0;
+    for (int k = total - 1; k >= total - t1; --k) s.put(lv[idx[k]] < 0 ? 1u : 0u, 1);
+    int sl = (total > 10 && t1 < 3) ? 1 : 0;
+    for (int k = total - 1 - t1; k >= 0; --k) {
+        const int v = lv[idx[k]];
+        int lc = v > 0 ? 2 * v - 2 : -2 * v - 1;
+        if (k == total - 1 - t1 && t1 < 3) lc -= 2;
+        int rest = -1;
+        if (sl == 0) {
+            if (lc < 14) s.put(1u, lc + 1);
+            else if (lc < 30) s.put(1u, 15), s.put((unsigned)(lc - 14), 4);
+            else rest = lc - 30;
+        } else {
+            if (lc < (15 << sl)) s.put(1u, (lc >> sl) + 1), s.put((unsigned)lc & ((1u << sl) - 1u), sl);
+            else rest = lc - (15 << sl);
+        }
+        if (rest >= 0) {
+            if (rest >= 4096) s.fail(), rest &= 4095;
+            s.put(1u, 16);
+            s.put((unsigned)rest, 12);
+        }
+        if (sl == 0) sl = 1;
+        if ((v < 0 ? -v : v) > (3 << (sl - 1)) && sl < 6) ++sl;
+    }
+    if (total < maxc) {
+        const int tz = idx[total - 1] + 1 - total;
+        h264_put_vlc(s, maxc == 4 ? kH264TotalZerosChromaDc + (total - 1) * 4 + tz : kH264TotalZeros + (total - 1) * 16 + tz);
+        int left = tz;
+        for (int k = total - 1; k > 0 && left > 0; --k) {
+            const int run = idx[k] - idx[k - 1] - 1;
+            h264_put_vlc(s, kH264RunBefore + ((left < 7 ? left : 7) - 1) * 16 + run);
+            left -= run;
+        }
+    }
+    return total;
+}
+
+H264_HD int h264_nc(int a, int b) {                     // -1 = not available
+    if (a >= 0 && b >= 0) return (a + b + 1) >> 1;
+    return a >= 0 ? a : b >= 0 ? b : 0;
+}
+
+// What a macroblock hands to its right neighbour in the slice: the reconstructed right columns, the AC TotalCoeff of its right blocks.
+struct h264_chain {
+    int have;
+    uint8_t ycol[16], ccol[2][8], tcy[4], tcc[2][2];
+};
+
+// Levels of one macroblock in coding order: block 0 Intra16x16DCLevel [16], 1..16 the luma AC blocks by luma4x4BlkIdx [15], 17 / 18 chroma
+// DC Cb / Cr [4], 19..26 chroma AC Cb 0..3, Cr 0..3 [15]; 16 int16 each, scan order.
+enum { kH264MbBlocks = 27, kH264MbLevels = 27 * 16 };
+
+H264_HD void h264_forward4x4(const int* x, int* w) {    // w = Cf x Cf^T, both [16] raster
+    int t[16];
+    for (int i = 0; i < 4; ++i) {
+        const int a = x[i * 4], b = x[i * 4 + 1], c = x[i * 4 + 2], d = x[i * 4 + 3];
+        t[i * 4] = a + b + c + d, t[i * 4 + 1] = 2 * a + b - c - 2 * d, t[i * 4 + 2] = a - b - c + d, t[i * 4 + 3] = a - 2 * b + 2 * c - d;
+    }
+    for (int j = 0; j < 4; ++j) {
+        const int a = t[j], b = t[4 + j], c = t[8 + j], d = t[12 + j];
+        w[j] = a + b + c + d, w[4 + j] = 2 * a + b - c - 2 * d, w[8 + j] = a - b - c + d, w[12 + j] = a - 2 * b + 2 * c - d;
+    }
+}
+H264_HD void h264_hadamard4x4(const int* x, int* y) {   // y = H x H, H = [1 1 1 1; 1 1 -1 -1; 1 -1 -1 1; 1 -1 1 -1]
+    int t[16];
+    for (int i = 0; i < 4; ++i) {
+        const int a = x[i * 4], b = x[i * 4 + 1], c = x[i * 4 + 2], d = x[i * 4 + 3];
+        t[i * 4] = a + b + c + d, t[i * 4 + 1] = a + b - c - d, t[i * 4 + 2] = a - b - c + d, t[i * 4 + 3] = a - b + c - d;
+    }
+    for (int j = 0; j < 4; ++j) {
+        const int a = t[j], b = t[4 + j], c = t[8 + j], d = t[12 + j];
+        y[j] = a + b + c + d, y[4 + j] = a + b - c - d, y[8 + j] = a - b - c + d, y[12 + j] = a - b + c - d;
+    }
+}
+H264_HD void h264_inverse4x4(const int* d, int* r) {    // 8.5.12.2: rows, columns, (x + 32) >> 6
+    int f[16];
+    for (int i = 0; i < 4; ++i) {
+        const int e0 = d[i * 4] + d[i * 4 + 2], e1 = d[i * 4] - d[i * 4 + 2], e2 = (d[i * 4 + 1] >> 1) - d[i * 4 + 3],
+                  e3 = d[i * 4 + 1] + (d[i * 4 + 3] >> 1);
+        f[i * 4] = e0 + e3, f[i * 4 + 1] = e1 + e2, f[i * 4 + 2] = e1 - e2, f[i * 4 + 3] = e0 - e3;
+    }
+    for (int j = 0; j < 4; ++j) {
+        const int e0 = f[j] + f[8 + j], e1 = f[j] - f[8 + j], e2 = (f[4 + j] >> 1) - f[12 + j], e3 = f[4 + j] + (f[12 + j] >> 1);
+        r[j] = (e0 + e3 + 32) >> 6, r[4 + j] = (e1 + e2 + 32) >> 6, r[8 + j] = (e1 - e2 + 32) >> 6, r[12 + j] = (e0 - e3 + 32) >> 6;
+    }
+}
+H264_HD int h264_quant(int w, int mf, int f, int qbits) {
+    const long long a = ((long long)(w < 0 ? -w : w) * mf + f) >> qbits;
+    return (int)(w < 0 ? -a : a);
+}
+H264_HD int h264_clip255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+// transform + quantise one 4x4 block of (src - pred); AC levels to lv[0..14] in scan order, returns the unquantised DC
+H264_HD int h264_block_levels(const uint8_t* src, int stride, int pred, int qp, int16_t* lv, bool* any_ac) {
+    int x[16], w[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) x[i * 4 + j] = (int)src[i * stride + j] - pred;
+    h264_forward4x4(x, w);
+    const int q6 = qp % 6, qbits = 15 + qp / 6, f = (1 << qbits) / 3;
+    for (int r = 1; r < 16; ++r) {
+        const int l = h264_quant(w[r], h264_mf(q6, h264_pos_class(r >> 2, r & 3)), f, qbits);
+        lv[h264_scan_pos(r) - 1] = (int16_t)l;
+        if (l) *any_ac = true;
+    }
+    return w[0];
+}
+// right column (4 samples) of the reconstruction of one block: AC levels lv[0..14] (scan order), dequantised DC dc
+H264_HD void h264_recon_column(const int16_t* lv, int dc, int pred, int qp, uint8_t* col) {
+    int d[16], r[16];
+    const int q6 = qp % 6, k = qp / 6;
+    d[0] = dc;
+    for (int p = 1; p < 16; ++p) {
+        const int ras = h264_zigzag(p);
+        d[ras] = (int)lv[p - 1] * h264_norm(q6, h264_pos_class(ras >> 2, ras & 3)) * (1 << k);
+    }
+    h264_inverse4x4(d, r);
+    for (int i = 0; i < 4; ++i) col[i] = (uint8_t)h264_clip255(pred + r[i * 4 + 3]);
+}
+
+// macroblock_layer() of one Intra16x16 macroblock from the levels; returns through the sink.  tcy / tcc receive the AC TotalCoeff.
+template <class Sink>
+H264_HD void h264_code_mb(const int16_t* lev, int cbp_luma, int cbp_chroma, const h264_chain& left, Sink& s, uint8_t* tcy, uint8_t* tcc) {
+    h264_put_ue(s, (unsigned)(1 + 2 + 4 * cbp_chroma + (cbp_luma ? 12 : 0)));
+    h264_put_ue(s, 0u);                                 // intra_chroma_pred_mode: DC
+    h264_put_se(s, 0);                                  // mb_qp_delta
+    for (int i = 0; i < 16; ++i) tcy[i] = 0;            // [by * 4 + bx]
+    for (int i = 0; i < 8; ++i) tcc[i] = 0;             // [c * 4 + by * 2 + bx]
+    h264_code_block(lev, 16, h264_nc(left.have ? left.tcy[0] : -1, -1), s);
+    if (cbp_luma)
+        for (int b = 0; b < 16; ++b) {
+            const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+            const int a = bx ? tcy[by * 4 + bx - 1] : left.have ? left.tcy[by] : -1;
+            const int t = by ? tcy[(by - 1) * 4 + bx] : -1;
+            tcy[by * 4 + bx] = (uint8_t)h264_code_block(lev + (1 + b) * 16, 15, h264_nc(a, t), s);
+        }
+    if (cbp_chroma)
+        for (int c = 0; c < 2; ++c) h264_code_block(lev + (17 + c) * 16, 4, -1, s);
+    if (cbp_chroma == 2)
+        for (int c = 0; c < 2; ++c)
+            for (int b = 0; b < 4; ++b) {
+                const int bx = b & 1, by = b >> 1;
+                const int a = bx ? tcc[c * 4 + by * 2] : left.have ? left.tcc[c][by] : -1;
+                const int t = by ? tcc[c * 4 + bx] : -1;
+                tcc[c * 4 + b] = (uint8_t)h264_code_block(lev + (19 + c * 4 + b) * 16, 15, h264_nc(a, t), s);
+            }
+}
+
+// One macroblock of the chain: sy [16 x 16], sc [2][8 x 8] source samples, lev scratch for kH264MbLevels levels.  Writes the macroblock
+// to w, updates the chain.  Returns 1 when it was coded I_PCM.
+H264_HD int h264_encode_mb(const uint8_t* sy, const uint8_t* sc, int16_t* lev, h264_chain& ch, int qp, h264_writer& w) {
+    const int q6 = qp % 6, qbits = 15 + qp / 6, f = (1 << qbits) / 3;
+    int pred_y = 128;
+    if (ch.have) {
+        int s = 8;
+        for (int i = 0; i < 16; ++i) s += ch.ycol[i];
+        pred_y = s >> 4;
+    }
+    for (int i = 0; i < kH264MbLevels; ++i) lev[i] = 0;
+    bool any_ac = false;
+    int dc[16], hd[16];
+    for (int b = 0; b < 16; ++b) {
+        const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+        dc[by * 4 + bx] = h264_block_levels(sy + by * 4 * 16 + bx * 4, 16, pred_y, qp, lev + (1 + b) * 16, &any_ac);
+    }
+    h264_hadamard4x4(dc, hd);
+    for (int r = 0; r < 16; ++r) lev[h264_scan_pos(r)] = (int16_t)h264_quant((hd[r] + 1) >> 1, h264_mf(q6, 0), 2 * f, qbits + 1);
+    const int qpc = h264_qpc(qp), c6 = qpc % 6, cbits = 15 + qpc / 6, fc = (1 << cbits) / 3;
+    int pred_c[2][2] = {{128, 128}, {128, 128}};        // [component][upper / lower half]
+    if (ch.have)
+        for (int c = 0; c < 2; ++c)
+            for (int h = 0; h < 2; ++h)
+                pred_c[c][h] = (ch.ccol[c][4 * h] + ch.ccol[c][4 * h + 1] + ch.ccol[c][4 * h + 2] + ch.ccol[c][4 * h + 3] + 2) >> 2;
+    bool any_cac = false, any_cdc = false;
+    for (int c = 0; c < 2; ++c) {
+        int d2[4];
+        for (int b = 0; b < 4; ++b)
+            d2[b] = h264_block_levels(sc + c * 64 + (b >> 1) * 4 * 8 + (b & 1) * 4, 8, pred_c[c][b >> 1], qpc, lev + (19 + c * 4 + b) * 16, &any_cac);
+        const int y2[4] = {d2[0] + d2[1] + d2[2] + d2[3], d2[0] - d2[1] + d2[2] - d2[3], d2[0] + d2[1] - d2[2] - d2[3], d2[0] - d2[1] - d2[2] + d2[3]};
+        for (int i = 0; i < 4; ++i) {
+            const int l = h264_quant(y2[i], h264_mf(c6, 0), 2 * fc, cbits + 1);
+            lev[(17 + c) * 16 + i] = (int16_t)l;
+            if (l) any_cdc = true;
+        }
+    }
+    const int cbp_luma = any_ac ? 15 : 0, cbp_chroma = any_cac ? 2 : any_cdc ? 1 : 0;
+    uint8_t tcy[16], tcc[8];
+    h264_counter cnt;
+    cnt.bits = 0, cnt.failed = false;
+    h264_code_mb(lev, cbp_luma, cbp_chroma, ch, cnt, tcy, tcc);
+    if (cnt.failed || cnt.bits > 3200) {                // Annex A.3.1 / level_prefix <= 15: I_PCM
+        h264_put_ue(w, 25u);
+        while (w.n) w.put(0u, 1);                       // pcm_alignment_zero_bit
+        for (int i = 0; i < 256; ++i) w.put(sy[i], 8);
+        for (int i = 0; i < 128; ++i) w.put(sc[i], 8);
+        for (int i = 0; i < 16; ++i) ch.ycol[i] = sy[i * 16 + 15];
+        for (int c = 0; c < 2; ++c)
+            for (int i = 0; i < 8; ++i) ch.ccol[c][i] = sc[c * 64 + i * 8 + 7];
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 16;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 16;
+        ch.have = 1;
+        return 1;
+    }
+    h264_code_mb(lev, cbp_luma, cbp_chroma, ch, w, tcy, tcc);
+    // reconstruction of what the chain reads: the right column of luma blocks (bx = 3) and of chroma blocks (bx = 1)
+    int c4[16], fm[16];
+    for (int r = 0; r < 16; ++r) c4[r] = lev[h264_scan_pos(r)];
+    h264_hadamard4x4(c4, fm);
+    const int k = qp / 6, v0 = h264_norm(q6, 0);
+    uint8_t ycol[16], ccol[2][8];
+    for (int by = 0; by < 4; ++by) {
+        const int fv = fm[by * 4 + 3];
+        const int dcy = k >= 2 ? fv * v0 * (1 << (k - 2)) : (fv * v0 + (1 << (1 - k))) >> (2 - k);
+        const int b = 8 * (by >> 1) + 2 * (by & 1) + 5;  // luma4x4BlkIdx of (bx 3, by): 5, 7, 13, 15
+        h264_recon_column(lev + (1 + b) * 16, dcy, pred_y, qp, ycol + 4 * by);
+    }
+    const int kc = qpc / 6, vc = h264_norm(c6, 0);
+    for (int c = 0; c < 2; ++c) {
+        const int16_t* d = lev + (17 + c) * 16;
+        const int f2[4] = {d[0] + d[1] + d[2] + d[3], d[0] - d[1] + d[2] - d[3], d[0] + d[1] - d[2] - d[3], d[0] - d[1] - d[2] + d[3]};
+        for (int by = 0; by < 2; ++by) {
+            const int dcc = (f2[by * 2 + 1] * vc * (1 << kc)) >> 1;
+            h264_recon_column(lev + (19 + c * 4 + by * 2 + 1) * 16, dcc, pred_c[c][by], qpc, ccol[c] + 4 * by);
+        }
+    }
+    for (int i = 0; i < 16; ++i) ch.ycol[i] = ycol[i];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 8; ++i) ch.ccol[c][i] = ccol[c][i];
+    for (int i = 0; i < 4; ++i) ch.tcy[i] = tcy[i * 4 + 3];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 2; ++i) ch.tcc[c][i] = tcc[c * 4 + i * 2 + 1];
+    ch.have = 1;
+    return 0;
+}
+
+template <class Sink>
+H264_HD void h264_slice_header(Sink& s, unsigned first_mb, unsigned idr_pic_id, int qp) {
+    h264_put_ue(s, first_mb);
+    h264_put_ue(s, 7u);                                 // slice_type: I, and every slice of the picture is
+    h264_put_ue(s, 0u);                                 // pic_parameter_set_id
+    s.put(0u, 4);                                       // frame_num
+    h264_put_ue(s, idr_pic_id);
+    s.put(0u, 2);                                       // no_output_of_prior_pics_flag, long_term_reference_flag
+    h264_put_se(s, qp - 26);                            // slice_qp_delta against pic_init_qp 26
+    h264_put_ue(s, 1u);                                 // disable_deblocking_filter_idc
+}

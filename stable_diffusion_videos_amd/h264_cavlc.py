@@ -1,0 +1,117 @@
+"""Entropy-coded H.264 video samples from frames that are already in HBM (csrc/sdv_h264.hip): the compressed counterpart of h264.py's
+``I_PCM`` pictures, for the mp4 of ``walk()``.
+
+The reference asks libx264 for ``crf 10, yuv420p`` (utils.py:69-128).  This is an all-intra, Constrained-Baseline, CAVLC stream with the
+same parameter sets as the ``I_PCM`` track (``h264.sps_pps``): every macroblock ``Intra16x16`` with DC prediction from its left neighbour,
+one IDR slice per macroblock row so that every row is an independent bit stream (one wave each on the GPU), ``I_PCM`` where a macroblock
+would break the 3200-bit limit of Annex A.3.1.  The stream rule is written down in include/sdv_hip.h and DESIGN.md ("H.264 CAVLC intra
+encoder"); tests/h264_ref.py restates it and decodes it.
+
+Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
+"""
+from __future__ import annotations
+
+from typing import Dict, List
+
+import torch
+
+from . import hip
+
+DEFAULT_QP = 16
+
+
+def check_qp(qp) -> int:
+    if isinstance(qp, bool) or not isinstance(qp, int) or not 0 <= qp <= 51:
+        raise ValueError(f"h264 qp must be an integer in 0 .. 51, got {qp!r}")
+    return qp
+
+
+class H264Encoder:
+    """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
+    (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.
+
+    Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
+    prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
+    capacity bound of sdv_hip.h, so no batch can fail to fit."""
+
+    def __init__(self, qp: int = DEFAULT_QP, device=None):
+        self.qp = check_qp(qp)
+        self.device = torch.device(device) if device is not None else None
+        self._ws: Dict[tuple, dict] = {}
+        self.last_bytes_to_host = 0
+
+    def _workspace(self, n: int, mbh: int, mbw: int, device) -> dict:
+        key = (n, mbh, mbw, str(device))
+        ws = self._ws.get(key)
+        if ws is None:
+            cap = hip.h264_out_bytes(n, mbh, mbw)
+            ws = dict(y=torch.empty((n, 16 * mbh, 16 * mbw), dtype=torch.uint8, device=device),
+                      cb=torch.empty((n, 8 * mbh, 8 * mbw), dtype=torch.uint8, device=device),
+                      cr=torch.empty((n, 8 * mbh, 8 * mbw), dtype=torch.uint8, device=device),
+                      scratch=torch.empty((hip.h264_scratch_bytes(n, mbh, mbw),), dtype=torch.uint8, device=device),
+                      out=torch.empty((cap,), dtype=torch.uint8, device=device),
+                      offsets=torch.zeros((n + 1,), dtype=torch.int64, device=device),
+                      offsets_host=torch.empty((n + 1,), dtype=torch.int64, pin_memory=True),
+                      out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True))
+            if len(self._ws) >= 4:                                                              # a walk uses one or two shapes
+                self._ws.pop(next(iter(self._ws)))
+            self._ws[key] = ws
+        return ws
+
+    def _check_device(self, what: str, t):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise hip.SdvHipError(f"H264Encoder.{what}: frames must live in GPU memory (got {getattr(t, 'device', type(t))}); "
+                                  "the HIP path has no CPU fallback")
+        if self.device is not None and self.device.index is not None and t.device != self.device:
+            raise hip.SdvHipError(f"H264Encoder.{what}: frames are on {t.device}, the encoder was made for {self.device}")
+
+    def encode(self, frames_u8: torch.Tensor, first_index: int = 0) -> List[bytes]:
+        self._check_device("encode", frames_u8)
+        if frames_u8.dtype != torch.uint8 or frames_u8.ndim != 4 or frames_u8.shape[-1] != 3:
+            raise hip.SdvHipError(f"H264Encoder.encode: expected a uint8 [n, H, W, 3] tensor, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        frames_u8 = frames_u8.contiguous()
+        n, H, W, _ = frames_u8.shape
+        if n == 0:
+            return []
+        if H % 2 or W % 2 or not (2 <= H <= hip.H264_MAX_DIM and 2 <= W <= hip.H264_MAX_DIM):
+            raise hip.SdvHipError(f"H264Encoder.encode: frame size must be even and 2 .. {hip.H264_MAX_DIM}, got {H} x {W}")
+        mbh, mbw = hip.h264_mb_grid(H, W)
+        with torch.cuda.device(frames_u8.device):
+            ws = self._workspace(n, mbh, mbw, frames_u8.device)
+            hip.h264_planes(frames_u8, ws["y"], ws["cb"], ws["cr"])
+            return self._rows_and_pack(ws, n, mbh, mbw, first_index)
+
+    def encode_planes(self, y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, first_index: int = 0) -> List[bytes]:
+        """The same from padded planes ``y [n, 16 mbh, 16 mbw]``, ``cb`` / ``cr [n, 8 mbh, 8 mbw]`` (any sample values)."""
+        for t in (y, cb, cr):
+            self._check_device("encode_planes", t)
+        if y.ndim != 3 or y.shape[0] == 0:
+            raise hip.SdvHipError(f"H264Encoder.encode_planes: expected y [n >= 1, 16 mbh, 16 mbw], got {tuple(y.shape)}")
+        n, mbh, mbw = y.shape[0], y.shape[1] // 16, y.shape[2] // 16
+        with torch.cuda.device(y.device):
+            ws = dict(self._workspace(n, mbh, mbw, y.device), y=y.contiguous(), cb=cb.contiguous(), cr=cr.contiguous())
+            return self._rows_and_pack(ws, n, mbh, mbw, first_index)
+
+    def _rows_and_pack(self, ws: dict, n: int, mbh: int, mbw: int, first_index: int) -> List[bytes]:
+        hip.h264_encode_rows(ws["y"], ws["cb"], ws["cr"], self.qp, int(first_index), ws["scratch"])
+        hip.h264_pack(ws["scratch"], n, mbh, mbw, ws["out"], ws["offsets"])
+        ws["offsets_host"].copy_(ws["offsets"], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        offs = ws["offsets_host"].tolist()
+        used = offs[n]
+        ws["out_host"][:used].copy_(ws["out"][:used], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        payload = ws["out_host"].numpy()
+        self.last_bytes_to_host = used + 8 * (n + 1)
+        return [payload[offs[k]:offs[k + 1]].tobytes() for k in range(n)]
+
+
+_encoders: Dict[tuple, H264Encoder] = {}
+
+
+def encoder_for(qp: int, device) -> H264Encoder:
+    """One cached encoder (and its workspaces) per quality setting and device."""
+    key = (check_qp(qp), str(device))
+    if key not in _encoders:
+        _encoders[key] = H264Encoder(qp, device)
+    return _encoders[key]

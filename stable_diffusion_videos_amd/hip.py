@@ -103,6 +103,10 @@ _SIGNATURES = {
                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "sdv_png_crc32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sdv_h264_planes_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 4),
+    "sdv_h264_encode_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "sdv_h264_pack": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sdv_h264_vlc_tables": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1424,3 +1428,146 @@ def png_crc32(out: torch.Tensor, offsets: torch.Tensor, needed: torch.Tensor, ac
     """Fill the IDAT CRC-32 of every file a packer left in ``out`` (``torch.ops.sdv.k_png_crc32`` -> sdv_png_crc32), in place; nothing
     happens when ``needed`` exceeds ``out.numel()``.  ``acc``: int32 [n] workspace."""
     _k_png_crc32(out, offsets, needed, acc)
+
+
+# ------------------------------------------------------------------------------------------------
+# H.264 CAVLC intra encoder (csrc/sdv_h264.hip; h264_cavlc.py holds the workspaces and cuts the samples)
+# ------------------------------------------------------------------------------------------------
+H264_MAX_DIM = 16384
+H264_VLC_WORDS = 656
+
+
+def h264_mb_grid(H: int, W: int):
+    return (int(H) + 15) // 16, (int(W) + 15) // 16
+
+
+def h264_slice_bytes(mbw: int) -> int:
+    """The most one slice of ``mbw`` macroblocks takes in a sample (sdv_hip.h "Capacity"): 4-byte length + NAL header + an RBSP of at
+    most 400 bytes per macroblock and 8 of header and stop bit, with an emulation-prevention byte behind every second byte."""
+    rbsp = 400 * int(mbw) + 8
+    return 5 + rbsp + rbsp // 2
+
+
+def h264_out_bytes(n: int, mbh: int, mbw: int) -> int:
+    """The capacity sdv_h264_pack demands of ``out``."""
+    return int(n) * int(mbh) * h264_slice_bytes(mbw)
+
+
+def h264_scratch_bytes(n: int, mbh: int, mbw: int) -> int:
+    """One slot per slice at an 8-byte stride, then an int64 start and an int32 length per slice."""
+    return int(n) * int(mbh) * (((h264_slice_bytes(mbw) + 7) & ~7) + 12)
+
+
+def _h264_u8(what, name, t, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "1-D" if shape is None else list(shape)
+        raise SdvHipError(f"{what}: {name} must be a contiguous uint8 {want} tensor, got {getattr(t, 'dtype', type(t))} "
+                          f"{tuple(getattr(t, 'shape', ()))}")
+
+
+def _h264_planes_impl(frames, y, cb, cr):
+    what = "h264_planes"
+    if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise SdvHipError(f"{what}: frames must be a contiguous uint8 [n, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    n, H, W, _ = frames.shape
+    if n < 1 or H % 2 or W % 2 or not (2 <= H <= H264_MAX_DIM and 2 <= W <= H264_MAX_DIM):
+        raise SdvHipError(f"{what}: frame size must be even, 2 .. {H264_MAX_DIM}, and n >= 1, got n={n} H={H} W={W}")
+    mbh, mbw = h264_mb_grid(H, W)
+    _h264_u8(what, "y", y, (n, 16 * mbh, 16 * mbw))
+    _h264_u8(what, "cb", cb, (n, 8 * mbh, 8 * mbw))
+    _h264_u8(what, "cr", cr, (n, 8 * mbh, 8 * mbw))
+    lib = load()
+    args = (_ptr(frames, name="frames"), n, H, W, _ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"))
+    _launch("h264_planes", dict(bytes=3.0 * n * H * W + 1.5 * y.numel()), lambda: _check(lib.sdv_h264_planes_u8(*args, _stream()), "sdv_h264_planes_u8"))
+
+
+_k_h264_planes = _defop("k_h264_planes(Tensor frames, Tensor(a!) y, Tensor(b!) cb, Tensor(c!) cr) -> ()", _h264_planes_impl)
+
+
+def h264_planes(frames: torch.Tensor, y: Optional[torch.Tensor] = None, cb: Optional[torch.Tensor] = None, cr: Optional[torch.Tensor] = None):
+    """uint8 RGB ``[n, H, W, 3]`` -> padded studio-range BT.601 planes ``y [n, 16 mbh, 16 mbw]``, ``cb`` / ``cr [n, 8 mbh, 8 mbw]`` by the
+    integer rule of sdv_hip.h (``torch.ops.sdv.k_h264_planes`` -> sdv_h264_planes_u8)."""
+    if frames.ndim == 4 and y is None:
+        mbh, mbw = h264_mb_grid(frames.shape[1], frames.shape[2])
+        y = torch.empty((frames.shape[0], 16 * mbh, 16 * mbw), dtype=torch.uint8, device=frames.device)
+        cb = torch.empty((frames.shape[0], 8 * mbh, 8 * mbw), dtype=torch.uint8, device=frames.device)
+        cr = torch.empty_like(cb)
+    _k_h264_planes(frames, y, cb, cr)
+    return y, cb, cr
+
+
+def _h264_plane_grid(what, y, cb, cr):
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.uint8 or y.ndim != 3 or not y.is_contiguous() or y.shape[0] < 1 \
+            or y.shape[1] % 16 or y.shape[2] % 16 or not y.shape[1] or not y.shape[2]:
+        raise SdvHipError(f"{what}: y must be a contiguous uint8 [n, 16 mbh, 16 mbw] tensor, got {getattr(y, 'dtype', type(y))} "
+                          f"{tuple(getattr(y, 'shape', ()))}")
+    n, mbh, mbw = y.shape[0], y.shape[1] // 16, y.shape[2] // 16
+    _h264_u8(what, "cb", cb, (n, 8 * mbh, 8 * mbw))
+    _h264_u8(what, "cr", cr, (n, 8 * mbh, 8 * mbw))
+    return n, mbh, mbw
+
+
+def _h264_encode_rows_impl(y, cb, cr, qp, first_index, scratch):
+    what = "h264_encode_rows"
+    n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if first_index < 0:
+        raise SdvHipError(f"{what}: first_index must be >= 0, got {first_index}")
+    _h264_u8(what, "scratch", scratch)
+    if scratch.ndim != 1 or scratch.numel() < h264_scratch_bytes(n, mbh, mbw):
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n * mbh} slices of {mbw} macroblocks need {h264_scratch_bytes(n, mbh, mbw)}")
+    lib = load()
+    args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(first_index) & 0x7fffffff,
+            _ptr(scratch, name="scratch"), scratch.numel())
+    _launch("h264_encode_rows", dict(bytes=1.5 * y.numel()), lambda: _check(lib.sdv_h264_encode_rows(*args, _stream()), "sdv_h264_encode_rows"))
+
+
+_k_h264_encode_rows = _defop("k_h264_encode_rows(Tensor y, Tensor cb, Tensor cr, int qp, int first_index, Tensor(a!) scratch) -> ()",
+                             _h264_encode_rows_impl)
+
+
+def h264_encode_rows(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, first_index: int, scratch: torch.Tensor):
+    """Code every macroblock row of every picture as one IDR slice into its slot of ``scratch`` (``h264_scratch_bytes``), by the stream
+    rule of sdv_hip.h (``torch.ops.sdv.k_h264_encode_rows`` -> sdv_h264_encode_rows).  Picture k carries idr_pic_id (first_index + k) & 1."""
+    _k_h264_encode_rows(y, cb, cr, int(qp), int(first_index), scratch)
+
+
+def _h264_pack_impl(scratch, n, mbh, mbw, out, offsets):
+    what = "h264_pack"
+    if n < 1 or not (1 <= mbh <= 1024 and 1 <= mbw <= 1024):
+        raise SdvHipError(f"{what}: macroblock grid must be 1 .. 1024 and n >= 1, got n={n} mbh={mbh} mbw={mbw}")
+    _h264_u8(what, "scratch", scratch)
+    if scratch.ndim != 1 or scratch.numel() < h264_scratch_bytes(n, mbh, mbw):
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n * mbh} slices of {mbw} macroblocks need {h264_scratch_bytes(n, mbh, mbw)}")
+    _h264_u8(what, "out", out)
+    if out.ndim != 1 or out.numel() < h264_out_bytes(n, mbh, mbw):
+        raise SdvHipError(f"{what}: out holds {out.numel()} bytes, the capacity bound of {n * mbh} slices of {mbw} macroblocks is "
+                          f"{h264_out_bytes(n, mbh, mbw)}")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.ndim != 1 or offsets.numel() != n + 1 or not offsets.is_contiguous():
+        raise SdvHipError(f"{what}: offsets must be a contiguous int64 vector of n + 1 = {n + 1} elements, got "
+                          f"{getattr(offsets, 'dtype', type(offsets))} x {getattr(offsets, 'numel', lambda: 0)()}")
+    lib = load()
+    args = (_ptr(scratch, name="scratch"), scratch.numel(), n, mbh, mbw, _ptr(out, name="out"), out.numel(), _ptr(offsets, name="offsets"))
+    _launch("h264_pack", dict(bytes=2.0 * out.numel()), lambda: _check(lib.sdv_h264_pack(*args, _stream()), "sdv_h264_pack"))
+
+
+_k_h264_pack = _defop("k_h264_pack(Tensor scratch, int n, int mbh, int mbw, Tensor(a!) out, Tensor(b!) offsets) -> ()", _h264_pack_impl)
+
+
+def h264_pack(scratch: torch.Tensor, n: int, mbh: int, mbw: int, out: torch.Tensor, offsets: torch.Tensor):
+    """Compact the slices ``h264_encode_rows`` left in ``scratch`` into ``out`` in sample order (``torch.ops.sdv.k_h264_pack`` ->
+    sdv_h264_pack): ``out[offsets[k]:offsets[k + 1]]`` is the mp4 sample of picture k.  ``out`` must hold ``h264_out_bytes``."""
+    _k_h264_pack(scratch, int(n), int(mbh), int(mbw), out, offsets)
+
+
+def _h264_vlc_tables_impl():
+    lib = load()
+    lengths, codes = (C.c_uint8 * H264_VLC_WORDS)(), (C.c_uint16 * H264_VLC_WORDS)()
+    _check(lib.sdv_h264_vlc_tables(lengths, codes, H264_VLC_WORDS), "sdv_h264_vlc_tables")
+    return list(zip(lengths, codes))
+
+
+def h264_vlc_tables():
+    """The kernel's VLC tables as 656 ``(length, code)`` pairs in the layout of sdv_hip.h (sdv_h264_vlc_tables; host only, no GPU work)."""
+    return _h264_vlc_tables_impl()

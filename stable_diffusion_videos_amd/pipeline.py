@@ -119,6 +119,8 @@ class StableDiffusionWalkPipeline:
         self.jpeg_quality = 75             # output_type="jpeg" and .jpg / .jpeg frame files (what PIL's Image.save writes for them)
         self.png_encoder = "pil"           # .png frame files: "pil" = Image.save on the host, "hip" = compressed in HBM (png.py); SDV_PNG wins
         self.png_matches = False           # the HIP PNG encoder's LZ77 matches and GPU-side CRC-32 (smaller files, more kernel time); SDV_PNG_MATCHES wins
+        self.video_codec = None            # the dependency-free mp4 writer's codec: None = video.py's default, "h264" / "mjpeg" / "h264-cavlc"; SDV_VIDEO_CODEC wins
+        self.h264_qp = 16                  # quantiser of the "h264-cavlc" track (0 .. 51; h264_cavlc.py); SDV_H264_QP wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
@@ -642,6 +644,20 @@ class StableDiffusionWalkPipeline:
             raise ValueError(f"SDV_PNG_MATCHES must be '1' or '0', got {env!r}")
         return env == "1"
 
+    def h264_qp_choice(self) -> int:
+        """The quantiser of the ``h264-cavlc`` video track: the environment variable SDV_H264_QP (an integer 0 .. 51) when it is set, else
+        ``self.h264_qp``."""
+        env = os.environ.get("SDV_H264_QP")
+        if env is None or env == "":
+            qp = self.h264_qp
+        elif env.isdigit():
+            qp = int(env)
+        else:
+            raise ValueError(f"SDV_H264_QP must be an integer 0 .. 51, got {env!r}")
+        if isinstance(qp, bool) or not isinstance(qp, int) or not 0 <= qp <= 51:
+            raise ValueError(f"SDV_H264_QP / h264_qp must be an integer 0 .. 51, got {qp!r}")
+        return qp
+
     def make_clip_frames(self, prompt_a: str, prompt_b: str, seed_a: int, seed_b: int, num_interpolation_steps: int = 5,
                          save_path: Union[str, Path] = "outputs/", num_inference_steps: int = 50,
                          guidance_scale: float = 7.5, eta: float = 0.0, height: Optional[int] = None,
@@ -872,10 +888,12 @@ class StableDiffusionWalkPipeline:
                 audio_offset = audio_start_sec + sum(num_interpolation_steps[:i]) / fps
                 make_video_pyav(c["save_path"], audio_filepath=audio_filepath, fps=fps, output_filepath=c["mp4"],
                                 glob_pattern=f"*{image_file_ext}", audio_offset=audio_offset,
-                                audio_duration=num_step / fps, sr=44100)                        # :787-796
+                                audio_duration=num_step / fps, sr=44100, codec=self.video_codec,
+                                h264_qp=self.h264_qp_choice())                                  # :787-796
             result = make_video_pyav(save_path_root, audio_filepath=audio_filepath, fps=fps, audio_offset=audio_start_sec,
                                      audio_duration=sum(num_interpolation_steps) / fps, output_filepath=output_filepath,
-                                     glob_pattern=f"**/*{image_file_ext}", sr=44100)             # :798-807
+                                     glob_pattern=f"**/*{image_file_ext}", sr=44100, codec=self.video_codec,
+                                     h264_qp=self.h264_qp_choice())                              # :798-807
         if world_size > 1:
             parallel.barrier()
             result = str(output_filepath) if result is None else result

@@ -10,8 +10,10 @@ they are not, a dependency-free writer produces a standards-conforming ISO-BMFF 
   * when an audio file is given, an uncompressed 16-bit PCM audio track of the same ``[audio_offset, audio_offset +
     audio_duration)`` window (sample entry ``ipcm`` + ``pcmC``, ISO/IEC 23003-5) where the reference has AAC,
 so that ``walk()`` returns the same ``{name}.mp4`` paths as the reference, in the reference's video codec and pixel format, and
-the music video still carries its music; entropy-coded H.264 and AAC need ffmpeg and are what this mode lacks.  Frames are
-read once each (the reference's pairwise ``torch.cat`` is O(n^2), :91-93).
+the music video still carries its music; entropy-coded H.264 and AAC need ffmpeg and are what this mode lacks by default.  Opt-in,
+``SDV_VIDEO_CODEC=h264-cavlc`` (or ``codec="h264-cavlc"``) writes an entropy-coded all-intra H.264 track compressed on the GPU
+(h264_cavlc.py, csrc/sdv_h264.hip) in the same ``avc1`` container.  Frames are read once each (the reference's pairwise ``torch.cat``
+is O(n^2), :91-93).
 """
 from __future__ import annotations
 
@@ -77,11 +79,21 @@ def _pcm16(audio, sr):
     return a16.tobytes(), int(a16.shape[0])
 
 
+def _pcm_samples(frames, width: int, height: int):
+    """The I_PCM track's samples (h264.py): one length-prefixed IDR slice NAL unit per frame."""
+    from . import h264
+    for k, fr in enumerate(frames):
+        assert fr.shape[:2] == (height, width), "all frames of a video have one size"
+        nal = h264.idr_picture(np.ascontiguousarray(fr[..., :3]), k)
+        yield struct.pack(">I", len(nal)) + nal
+
+
 def write_h264_mp4(frames, width: int, height: int, fps: float, path: Union[str, Path],
-                   audio: Optional[np.ndarray] = None, sr: int = 44100) -> str:
+                   audio: Optional[np.ndarray] = None, sr: int = 44100, samples=None) -> str:
     """ISO base media file with an H.264 video track (sample entry ``avc1`` + ``avcC``; every sample one IDR picture of I_PCM
     macroblocks, h264.py) and the optional PCM audio track: ftyp | mdat (64-bit size; length-prefixed NAL units streamed to disk
-    frame by frame, then the PCM samples) | moov.  ``frames``: iterable of uint8 RGB [H, W, 3]."""
+    frame by frame, then the PCM samples) | moov.  ``frames``: iterable of uint8 RGB [H, W, 3].  ``samples``: an iterable of ready-made
+    samples (each the length-prefixed NAL units of one picture, coded against ``h264.sps_pps``; h264_cavlc.py) instead of ``frames``."""
     from . import h264
     timescale = 90000
     delta = int(round(timescale / float(fps)))
@@ -93,11 +105,9 @@ def write_h264_mp4(frames, width: int, height: int, fps: float, path: Union[str,
     sizes = []
     with open(path, "wb") as f:
         f.write(ftyp + struct.pack(">I4sQ", 1, b"mdat", 0))            # largesize patched below
-        for k, fr in enumerate(frames):
-            assert fr.shape[:2] == (height, width), "all frames of a video have one size"
-            nal = h264.idr_picture(np.ascontiguousarray(fr[..., :3]), k)
-            f.write(struct.pack(">I", len(nal)) + nal)
-            sizes.append(4 + len(nal))
+        for sample in (samples if samples is not None else _pcm_samples(frames, width, height)):
+            f.write(sample)
+            sizes.append(len(sample))
         n, video_bytes = len(sizes), sum(sizes)
         f.write(pcm)
         duration = n * delta
@@ -204,8 +214,11 @@ LAST_CODEC: dict = {}
 
 def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./images", audio_filepath=None, fps: int = 30,
                     audio_offset: int = 0, audio_duration: int = 2, sr: int = 22050,
-                    output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png"):
-    """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it."""
+                    output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png", codec: Optional[str] = None,
+                    h264_qp: Optional[int] = None):
+    """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it.  ``codec``: what
+    ``SDV_VIDEO_CODEC`` selects (the variable wins): ``"h264"`` (I_PCM), ``"mjpeg"`` or ``"h264-cavlc"`` - the entropy-coded intra
+    stream of h264_cavlc.py at quantiser ``h264_qp`` (0 .. 51, default 16), compressed in GPU memory."""
     output_filepath = str(output_filepath)
     gpu_frames = None                      # a uint8 tensor in GPU memory: a Motion-JPEG track is compressed there (jpeg.py)
     if isinstance(frames_or_frame_dir, torch.Tensor) and frames_or_frame_dir.is_cuda and frames_or_frame_dir.dtype == torch.uint8 \
@@ -236,11 +249,25 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
         LAST_CODEC.update(path=output_filepath, video="h264 (libx264)", audio="aac" if audio_filepath else None, why="torchvision / pyav present")
         return output_filepath
     audio = None
-    why = "SDV_VIDEO_CODEC" if os.environ.get("SDV_VIDEO_CODEC") else "default"
-    codec = (os.environ.get("SDV_VIDEO_CODEC") or DEFAULT_CODEC).lower()
-    if codec not in ("h264", "mjpeg"):
-        raise ValueError(f"SDV_VIDEO_CODEC={codec!r}: expected 'h264' or 'mjpeg'")
+    why = "SDV_VIDEO_CODEC" if os.environ.get("SDV_VIDEO_CODEC") else "codec argument" if codec else "default"
+    codec = (os.environ.get("SDV_VIDEO_CODEC") or codec or DEFAULT_CODEC).lower()
+    if codec not in ("h264", "mjpeg", "h264-cavlc"):
+        raise ValueError(f"SDV_VIDEO_CODEC={codec!r}: expected 'h264', 'mjpeg' or 'h264-cavlc'")
     h, w = frames[0].shape[:2] if frames is not None else (int(gpu_frames.shape[1]), int(gpu_frames.shape[2]))
+    cavlc_device = None
+    if codec == "h264-cavlc":
+        from .h264_cavlc import DEFAULT_QP, check_qp
+        qp = check_qp(DEFAULT_QP if h264_qp is None else h264_qp)
+        if h % 2 or w % 2:
+            codec = "h264"                                                                     # (the odd-size rule below sends it to Motion-JPEG)
+        elif gpu_frames is not None:
+            cavlc_device = gpu_frames.device
+        elif torch.cuda.is_available():
+            cavlc_device = torch.device("cuda", torch.cuda.current_device())
+        else:
+            logger.warning("h264-cavlc needs a GPU and none is present: writing the uncompressed I_PCM H.264 track instead")
+            codec = "h264"
+            why = "h264-cavlc asked for, no GPU present: I_PCM fallback"
     if codec == "h264":
         est = n_frames * (w * h * 3 // 2)
         if est > H264_PCM_MAX_BYTES and not os.environ.get("SDV_VIDEO_CODEC"):
@@ -260,8 +287,23 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
         logger.warning("no ffmpeg/pyav in this environment: the audio track is uncompressed 16-bit PCM instead of AAC")
         audio, _ = load_audio(audio_filepath, sr=sr, mono=True, offset=audio_offset, duration=audio_duration)
     LAST_CODEC.clear()
-    LAST_CODEC.update(path=output_filepath, video="h264 (I_PCM)" if codec == "h264" else "mjpeg", audio="pcm_s16le" if audio is not None else None,
-                      why=why)
+    LAST_CODEC.update(path=output_filepath, video={"h264": "h264 (I_PCM)", "h264-cavlc": "h264 (CAVLC intra)"}.get(codec, "mjpeg"),
+                      audio="pcm_s16le" if audio is not None else None, why=why)
+    if codec == "h264-cavlc":
+        from .h264_cavlc import encoder_for as h264_encoder_for
+        enc = h264_encoder_for(qp, cavlc_device)
+        step = max(1, (64 << 20) // (h * w * 3))                                            # batches of about 64 MB of raw frames
+
+        def cavlc_samples():
+            for k in range(0, n_frames, step):
+                if gpu_frames is not None:
+                    batch = gpu_frames[k:k + step]
+                else:                                                                       # a frame directory or CPU tensor: uploaded in batches
+                    batch = torch.from_numpy(np.stack([np.ascontiguousarray(fr[..., :3]) for fr in frames[k:k + step]])).to(cavlc_device)
+                assert tuple(batch.shape[1:3]) == (h, w), "all frames of a video have one size"
+                yield from enc.encode(batch.contiguous(), first_index=k)
+
+        return write_h264_mp4(None, w, h, fps, output_filepath, audio=audio, sr=sr, samples=cavlc_samples())
     if codec == "h264":
         return write_h264_mp4(frames if frames is not None else _frames_uint8(frames_or_frame_dir, glob_pattern), w, h, fps, output_filepath,
                               audio=audio, sr=sr)

@@ -1,0 +1,150 @@
+"""GPU H.264 CAVLC intra encoder (h264_cavlc.H264Encoder) against the two video tracks it can stand in for, on the same box.
+
+    python tools/h264_bench.py [--out FILE] [--reps 5]
+
+Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
+weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
+noise (the worst case).  Per case:
+  * frames/s of encode() at qp 16 on frames already in HBM - HIP events and the host clock around the call, copies back included
+    (encode() ends in a synchronise) - and of its three entry points alone;
+  * frames/s of the host ``I_PCM`` writer (h264.idr_picture, one thread, as video.write_h264_mp4 runs it) after the raw copy it needs,
+    and of the Motion-JPEG branch on the GPU (jpeg encoder, quality 95);
+  * bytes per frame at qp 10 / 16 / 22 against I_PCM and Motion-JPEG q95;
+  * at 512 x 512, Y-PSNR of the reconstruction at qp 10 / 16 / 22: the first frame's sample decoded by the decoder of
+    tests/h264_ref.py against the integer-rule Y' of the source.
+There is no fallback: without a GPU this tool fails.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import platform
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+QPS = (10, 16, 22)
+
+
+def pipeline_frames(pipe, n: int, batch: int = 16) -> torch.Tensor:
+    """n frames of 512 x 512 from the tiny pipeline, uint8 NHWC in GPU memory."""
+    T = np.linspace(0.0, 1.0, n)
+    out = []
+    for _, embeds, noise in pipe.generate_inputs("a cat", "a dog", 42, 1337, (1, 4, 64, 64), T, batch):
+        out.append(pipe(latents=noise, text_embeddings=embeds, height=512, width=512, num_inference_steps=4, output_type="u8_cuda")["images"].clone())
+    return torch.cat(out)
+
+
+def timed(fn, reps: int):
+    """(median HIP-event ms, median host-clock ms) of fn() after two warm-up calls."""
+    fn(), fn()
+    gpu_ms, wall_ms = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        wall_ms.append((time.perf_counter() - t0) * 1e3)
+        gpu_ms.append(e0.elapsed_time(e1))
+    return float(np.median(gpu_ms)), float(np.median(wall_ms))
+
+
+def measure(name: str, dev_frames: torch.Tensor, reps: int) -> dict:
+    import h264_ref as R
+    from stable_diffusion_videos_amd import h264, hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    from stable_diffusion_videos_amd.jpeg import encoder_for as jpeg_encoder_for
+    n, H, W, _ = dev_frames.shape
+    mbh, mbw = hip.h264_mb_grid(H, W)
+    case = dict(content=name, n=n, H=H, W=W)
+    enc = H264Encoder(16, dev_frames.device)
+    ev, wall = timed(lambda: enc.encode(dev_frames), reps)
+    case.update(cavlc_encode_ms_events=round(ev, 3), cavlc_encode_ms_host_clock=round(wall, 3), cavlc_frames_per_sec=round(n / wall * 1e3, 1),
+                cavlc_bytes_to_host_per_frame=int(enc.last_bytes_to_host // n))
+    ws = next(iter(enc._ws.values()))
+    stages = (("planes", lambda: hip.h264_planes(dev_frames, ws["y"], ws["cb"], ws["cr"])),
+              ("rows", lambda: hip.h264_encode_rows(ws["y"], ws["cb"], ws["cr"], 16, 0, ws["scratch"])),
+              ("pack", lambda: hip.h264_pack(ws["scratch"], n, mbh, mbw, ws["out"], ws["offsets"])))
+    for stage, fn in stages:
+        case[f"cavlc_{stage}_kernel_ms"] = round(timed(fn, reps)[0], 3)
+    jenc = jpeg_encoder_for(95, dev_frames.device)
+    ev, wall = timed(lambda: jenc.encode(dev_frames), reps)
+    jpegs = jenc.encode(dev_frames)
+    case.update(mjpeg_q95_encode_ms_host_clock=round(wall, 3), mjpeg_q95_frames_per_sec=round(n / wall * 1e3, 1),
+                mjpeg_q95_bytes_per_frame=int(sum(len(j) for j in jpegs) // n))
+    pinned = torch.empty(dev_frames.shape, dtype=torch.uint8, pin_memory=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pinned.copy_(dev_frames, non_blocking=True)
+    torch.cuda.synchronize()
+    copy_ms = (time.perf_counter() - t0) * 1e3
+    host = pinned.numpy()
+    k = min(n, 8)
+    pcm_ms = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        sizes = [4 + len(h264.idr_picture(host[i], i)) for i in range(k)]
+        pcm_ms.append((time.perf_counter() - t0) * 1e3 / k)
+    per_frame = min(pcm_ms) + copy_ms / n
+    case.update(pcm_host_ms_per_frame_incl_copy=round(per_frame, 3), pcm_host_frames_per_sec=round(1e3 / per_frame, 1), pcm_bytes_per_frame=int(sizes[0]),
+                raw_copy_ms=round(copy_ms, 3))
+    case["cavlc_vs_pcm_host_speed"] = round(case["cavlc_frames_per_sec"] / case["pcm_host_frames_per_sec"], 2)
+    case["cavlc_vs_mjpeg_gpu_speed"] = round(case["cavlc_frames_per_sec"] / case["mjpeg_q95_frames_per_sec"], 2)
+    for qp in QPS:
+        samples = H264Encoder(qp, dev_frames.device).encode(dev_frames)
+        size = int(sum(len(s) for s in samples) // n)
+        case[f"cavlc_qp{qp}_bytes_per_frame"] = size
+        case[f"cavlc_qp{qp}_vs_pcm_bytes"] = round(size / case["pcm_bytes_per_frame"], 4)
+        case[f"cavlc_qp{qp}_vs_mjpeg_q95_bytes"] = round(size / case["mjpeg_q95_bytes_per_frame"], 3)
+        if H * W <= 512 * 512:
+            d = R.decode_sample(samples[0], W, H)
+            y = R.rgb_to_planes(host[:1])[0][0, :H, :W].astype(np.float64)
+            mse = float(np.mean((d["y"].astype(np.float64) - y) ** 2))
+            case[f"cavlc_qp{qp}_y_psnr_db"] = round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None
+            case[f"cavlc_qp{qp}_pcm_macroblocks_frame0"] = int(d["n_pcm"])
+    print(json.dumps(case), flush=True)
+    return case
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("h264_bench needs the GPU (no fallback)")
+    from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
+    from stable_diffusion_videos_amd.upsampling import RealESRGANModel
+    dev = torch.device("cuda", 0)
+    result = dict(tool="tools/h264_bench.py", gpu=torch.cuda.get_device_name(0), host=platform.processor() or platform.machine(), reps=args.reps,
+                  qp_timed=16, cases=[])
+    pipe = StableDiffusionWalkPipeline.from_pretrained("tiny").to(dev)
+    small = pipeline_frames(pipe, 128)
+    up = RealESRGANModel.from_pretrained("nateraw/real-esrgan")
+    up.to(dev)
+    big = torch.cat([up.upsample_u8(small[k:k + 2]) for k in range(0, 8, 2)])
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    for name, frames in (("tiny pipeline", small), ("uniform noise", torch.randint(0, 256, (128, 512, 512, 3), dtype=torch.uint8, generator=gen).to(dev)),
+                         ("tiny pipeline x4 upsampler", big),
+                         ("uniform noise", torch.randint(0, 256, (8, 2048, 2048, 3), dtype=torch.uint8, generator=gen).to(dev))):
+        result["cases"].append(measure(name, frames.contiguous(), args.reps))
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
