@@ -555,6 +555,51 @@ int sdv_h264_pack(void* scratch, int64_t scratch_bytes, int32_t n, int32_t mbh, 
                   int64_t* offsets, void* stream);
 int sdv_h264_vlc_tables(uint8_t* host_lengths, uint16_t* host_codes, int32_t count);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * H.264 P pictures (zero-motion inter prediction) for the CAVLC encoder above.  One additive entry point (51 with it; the ABI version
+ * stays 12); opt-in (h264_cavlc.H264Encoder(gop=...), video.py: SDV_H264_GOP), gop 1 runs sdv_h264_encode_rows and writes its bytes.
+ *
+ * Stream rule.  Setting gop, an integer 1 .. 256.  Within one call picture k (position in the call) is an IDR picture iff k % gop == 0,
+ * coded exactly as above (slice header, idr_pic_id = (first_index + k) & 1, frame_num 0); the others are P pictures.  Every call
+ * starts a new GOP: no reference crosses a call.  Parameter sets unchanged (max_num_ref_frames 1, one active reference, POC type 2,
+ * frame_num u(4)).
+ *   P picture: one slice NAL unit per macroblock row, NAL header 0x41 (nal_ref_idc 2, type 1).  Slice header: first_mb_in_slice =
+ *   row * mbw, slice_type 5, pic_parameter_set_id 0, frame_num = (k % gop) & 15, num_ref_idx_active_override_flag 0,
+ *   ref_pic_list_modification_flag_l0 0, adaptive_ref_pic_marking_mode_flag 0, slice_qp_delta = qp - 26,
+ *   disable_deblocking_filter_idc 1.  Slice data: mb_skip_run before every coded macroblock, and once more at the end of a slice that
+ *   ends in skipped macroblocks.  Every vector is (0, 0): the row above is unavailable, so the predictor is (0, 0) and P_Skip infers it.
+ *   Mode (luma only): sad_inter = sum |src - ref| over the co-located 16 x 16 of the previous picture's reconstruction, sad_intra =
+ *   sum |src - DC| with the Intra16x16 DC predictor (128 at the start of a row); intra iff sad_intra < sad_inter, else inter.
+ *   Inter: residual src - ref; every luma 4x4 block 16 coefficients (no DC transform); chroma as above (2x2 Hadamard of the DCs, 15
+ *   AC).  Quantisation as above with f = (1 << qbits) / 6 (DC blocks 2 f, qbits + 1).  cbp luma bit b set iff any level of 8x8 block b
+ *   is nonzero, chroma 0 / 1 / 2 as above.  cbp 0: P_Skip.  Else P_L0_16x16: mb_type ue(0), mvd_l0 se(0) se(0), coded_block_pattern
+ *   me(v) by the inter column of Table 9-4 (codeNum -> cbp: 0 16 1 2 4 8 32 3 5 10 12 15 47 7 11 13 14 6 9 31 35 37 42 44 33 34 36 40
+ *   39 43 45 46 17 18 20 24 19 21 26 28 23 27 29 30 22 25 38 41), mb_qp_delta se(0), residual: luma blocks by luma4x4BlkIdx in the 8x8s
+ *   whose cbp bit is set (maxNumCoeff 16), chroma DC, chroma AC.
+ *   nC as in 9.2.1: an uncoded or skipped block counts 0, an inter block its 16-coefficient TotalCoeff, an Intra16x16 block its AC
+ *   TotalCoeff, I_PCM 16.
+ *   Intra in a P slice: as in an IDR slice with mb_type ue(5 + intra mb_type); constrained_intra_pred_flag is 0, the left neighbour's
+ *   reconstruction is used whatever its mode.  I_PCM: mb_type ue(30), by the same two triggers (macroblock_layer() above 3200 bits, or
+ *   level_prefix > 15).
+ *   Reconstruction per 8.5 of ALL samples of every macroblock (IDR pictures included; P_Skip copies the reference, I_PCM the source)
+ *   into the planes ry / rcb / rcr: picture k's reference is picture k - 1 of them.  All integer: it is the decoder's picture.
+ *
+ * Capacity of the GOP path.  first_mb_in_slice < 2^20 takes at most 41 bits, so a P slice header takes at most 41 + 5 + 1 + 4 + 3 + 11 +
+ * 3 = 68 bits (an IDR one 41 + 7 + 1 + 4 + 3 + 2 + 11 + 3 = 72); an mb_skip_run (< 1024) at most 21 bits; a coded macroblock at most
+ * 3200 bits (I_PCM in a P slice 9 + 7 + 3072).  With one run per macroblock, the trailing run, the stop bit and 7 alignment zeros a
+ * slice's RBSP takes at most (68 + 3221 mbw + 21 + 8 + 7) / 8 <= 403 mbw + 13 bytes, with emulation prevention, NAL header and length
+ * at most 5 + 3 (403 mbw + 13) / 2 <= 604.5 mbw + 25 bytes.  That is above the intra slot, so the GOP path takes the slots of a
+ * picture   mbw' = mbw + 1 + mbw / 64   macroblocks wide: 600 mbw' + 17 >= 600 mbw + 617 + 600 (mbw / 64 - 63 / 64) > 604.5 mbw + 25
+ * for every mbw >= 1.  Scratch and output are those of the intra path at (n, mbh, mbw'), so sdv_h264_pack(scratch, n, mbh, mbw', ...)
+ * packs them; mbw' <= 1024 limits the GOP path to mbw <= 1008.  The writer checks every store against its slot whatever the input.
+ *
+ * sdv_h264_encode_gops    planes as for sdv_h264_encode_rows; ry (16-byte aligned) / rcb / rcr (8-byte) uint8 in the planes' layout,
+ *   written whole; scratch_bytes >= that of (n, mbh, mbw').  One launch, one wave per (GOP, macroblock row), the macroblock's 24 4x4
+ *   blocks one lane each. */
+int sdv_h264_encode_gops(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, int32_t n, int32_t mbh, int32_t mbw, int32_t qp,
+                         int32_t gop, int32_t first_index, uint8_t* ry, uint8_t* rcb, uint8_t* rcr, void* scratch, int64_t scratch_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
 //   sdv_h264_planes_u8     frames -> Y / Cb / Cr planes, integer BT.601, edge-replicated to whole macroblocks
 //   sdv_h264_encode_rows   planes -> one complete slice (4-byte length | NAL header | payload with emulation prevention) per macroblock
 //                          row and frame, each in its own slot of the scratch buffer, plus its length
+//   sdv_h264_encode_gops   planes -> the same slots, but picture k of a call is an IDR picture only when k % gop == 0 and a P picture
+//                          (zero-motion inter prediction from the reconstruction of picture k - 1) otherwise; reconstruction planes
 //   sdv_h264_pack          slots -> one contiguous buffer in sample order, and offsets[n + 1]
 //   sdv_h264_vlc_tables    host only: the VLC tables of the kernel as (length, code) pairs
 //
@@ -11,6 +13,11 @@
 // samples in LDS with 16- and 8-byte loads, lane 0 walks the chain (sdv_h264_core.h: transform, quantisation, CAVLC, the I_PCM decision,
 // reconstruction of the right columns) with the levels in LDS.  The chains of a batch (4096 at 128 frames of 512 x 512) fill the GPU's
 // wave slots; the work inside a chain is not spread over the lanes.
+//
+// GOP path: row r of picture k reads row r of the reconstruction of picture k - 1, so a chain is a (GOP, row) and there are gop times
+// fewer of them.  One wave per chain again, but the macroblock's work is spread over its lanes: one 4x4 block per lane (16 luma, 8
+// chroma) for SAD, residual, transform, quantisation and reconstruction, "any level nonzero" by ballot, levels and reconstruction in
+// LDS; lane 0 keeps the DC blocks, the counting pass, the I_PCM decision and the bit writing.
 #include "sdv_common.h"
 #include "sdv_h264_core.h"
 
@@ -86,6 +93,95 @@ __global__ __launch_bounds__(64) void h264_rows_kernel(const uint8_t* __restrict
     }
 }
 
+SDV_DEVICE int h264_wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// One wave per (GOP, macroblock row): the GOP's pictures in order, in each the row's macroblocks.  ry / rcb / rcr are written by this
+// wave for picture k and read back by it for picture k + 1 (the fence between two pictures orders the two).
+__global__ __launch_bounds__(64) void h264_gops_kernel(const uint8_t* __restrict__ y, const uint8_t* __restrict__ cb, const uint8_t* __restrict__ cr,
+                                                       int n, int mbh, int mbw, int qp, int gop, int first_index, uint8_t* ry, uint8_t* rcb,
+                                                       uint8_t* rcr, uint8_t* __restrict__ slots, long long stride, long long slot_bytes,
+                                                       int32_t* __restrict__ lens) {
+    __shared__ h264_gop_mb mb;
+    const int lane = threadIdx.x;
+    const int r = (int)(blockIdx.x % mbh);
+    const long long g = blockIdx.x / mbh;
+    const long long lw = (long long)mbw * 16, cw = (long long)mbw * 8;
+    h264_writer w;
+    h264_chain ch;
+    int skip_run = 0;
+    w.init(slots, 0);
+    ch.have = 0;
+    for (int k = 0; k < gop; ++k) {
+        const long long f = g * gop + k;
+        if (f >= n) break;
+        const bool p = k > 0;
+        const long long row = f * mbh + r;
+        uint8_t* slot = slots + row * stride;
+        if (lane == 0) {
+            w.init(slot + 5, slot_bytes - 5);
+            ch.have = 0;
+            skip_run = 0;
+            if (p) h264_p_slice_header(w, (unsigned)(r * mbw), (unsigned)k, qp);
+            else h264_slice_header(w, (unsigned)(r * mbw), (unsigned)((first_index + f) & 1), qp);
+        }
+        const long long yat = row * 16 * lw, cat = row * 8 * cw;                   // this row in picture f; picture f - 1 lies mbh rows before
+        const long long yref = yat - (long long)mbh * 16 * lw, cref = cat - (long long)mbh * 8 * cw;
+        for (int m = 0; m < mbw; ++m) {
+            if (lane < 16) {
+                *(uint4*)(mb.sy + lane * 16) = *(const uint4*)(y + yat + lane * lw + m * 16);
+                if (p) *(uint4*)(mb.fy + lane * 16) = *(const uint4*)(ry + yref + lane * lw + m * 16);
+            } else if (lane < 32) {
+                const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+                *(uint2*)(mb.sc + c * 64 + i * 8) = *(const uint2*)((c ? cr : cb) + cat + i * cw + m * 8);
+                if (p) *(uint2*)(mb.fc + c * 64 + i * 8) = *(const uint2*)((c ? rcr : rcb) + cref + i * cw + m * 8);
+            }
+            if (lane == 0) h264_gop_pred(&mb, ch);
+            __syncthreads();
+            bool inter = false;
+            if (p) {
+                int si = 0, sp = 0;
+                if (lane < 16) h264_gop_block_sad(&mb, lane, &si, &sp);
+                si = h264_wave_sum(si), sp = h264_wave_sum(sp);
+                inter = !(si < sp);
+            }
+            const bool mine = lane < 24 && h264_gop_block_forward(&mb, lane, inter, qp);
+            const unsigned nz = (unsigned)__ballot(mine);
+            __syncthreads();
+            if (lane == 0) {
+                const bool any_cdc = h264_gop_dc(&mb, inter, qp);
+                h264_gop_serial(&mb, nz, any_cdc, inter, p, ch, w, &skip_run);
+            }
+            __syncthreads();
+            if (lane < 24) h264_gop_block_recon(&mb, lane, qp);
+            __syncthreads();
+            if (lane < 16) {
+                *(uint4*)(ry + yat + lane * lw + m * 16) = *(const uint4*)(mb.ry + lane * 16);
+            } else if (lane < 32) {
+                const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+                *(uint2*)((c ? rcr : rcb) + cat + i * cw + m * 8) = *(const uint2*)(mb.rc + c * 64 + i * 8);
+            }
+            if (lane == 0) h264_gop_chain(&mb, ch);
+            __syncthreads();
+        }
+        if (lane == 0) {
+            if (p && skip_run) h264_put_ue(w, (unsigned)skip_run);                 // the slice ends in skipped macroblocks
+            w.put(1u, 1);                               // rbsp_slice_trailing_bits
+            while (w.n) w.put(0u, 1);
+            const long long used = min(w.pos, slot_bytes - 5);      // (the capacity bound keeps pos below it; nothing was stored beyond)
+            const unsigned len = (unsigned)(1 + used);
+            slot[0] = (uint8_t)(len >> 24), slot[1] = (uint8_t)(len >> 16), slot[2] = (uint8_t)(len >> 8), slot[3] = (uint8_t)len;
+            slot[4] = p ? 0x41 : 0x65;                  // nal_ref_idc 2, nal_unit_type 1 | nal_ref_idc 3, nal_unit_type 5
+            lens[row] = (int32_t)(5 + used);
+        }
+        __threadfence();                                // the reconstruction of picture f is the reference of picture f + 1
+        __syncthreads();
+    }
+}
+
 // ONE workgroup: exclusive scan of the slice lengths, frame-major -> starts[row], offsets[frame], offsets[n]
 __global__ __launch_bounds__(kThreads) void h264_scan_kernel(const int32_t* __restrict__ lens, long long* __restrict__ starts, long long rows, int mbh,
                                                              long long* __restrict__ offsets) {
@@ -142,6 +238,10 @@ h264_layout h264_scratch_layout(int n, int mbh, int mbw) {
     return l;
 }
 
+// The GOP path's slots are those of a picture this many macroblocks wide (sdv_hip.h "Capacity of the GOP path"), so that sdv_h264_pack
+// reads them with the same layout.
+int h264_gop_slot_mbw(int mbw) { return mbw + 1 + mbw / 64; }
+
 }  // namespace
 
 #define H264_GRID_ARGS(name)                                                                                                       \
@@ -176,6 +276,30 @@ extern "C" int sdv_h264_encode_rows(const uint8_t* y, const uint8_t* cb, const u
     hipLaunchKernelGGL(h264_rows_kernel, dim3((unsigned)l.rows), dim3(64), 0, (hipStream_t)stream, y, cb, cr, mbh, mbw, qp, first_index, base, l.stride,
                        l.slot, (int32_t*)(base + l.lens_at));
     SDV_CHECK_LAUNCH("sdv_h264_encode_rows");
+    return SDV_OK;
+}
+
+extern "C" int sdv_h264_encode_gops(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, int32_t n, int32_t mbh, int32_t mbw, int32_t qp,
+                                    int32_t gop, int32_t first_index, uint8_t* ry, uint8_t* rcb, uint8_t* rcr, void* scratch,
+                                    int64_t scratch_bytes, void* stream) {
+    SDV_REQUIRE(y && cb && cr && ry && rcb && rcr && scratch, "sdv_h264_encode_gops: null pointer");
+    H264_GRID_ARGS("sdv_h264_encode_gops");
+    SDV_REQUIRE(mbw <= 1008, "sdv_h264_encode_gops: mbw=%d above 1008 (its slots are those of a wider picture, which must stay within 1024)", mbw);
+    SDV_REQUIRE(qp >= 0 && qp <= 51, "sdv_h264_encode_gops: qp=%d outside 0 .. 51", qp);
+    SDV_REQUIRE(gop >= 1 && gop <= kH264GopMax, "sdv_h264_encode_gops: gop=%d outside 1 .. %d", gop, (int)kH264GopMax);
+    SDV_REQUIRE(first_index >= 0, "sdv_h264_encode_gops: negative first_index");
+    const h264_layout l = h264_scratch_layout(n, mbh, h264_gop_slot_mbw(mbw));
+    SDV_REQUIRE(scratch_bytes >= l.bytes, "sdv_h264_encode_gops: scratch buffer too small: %lld bytes, %lld slices of %d macroblocks need %lld",
+                (long long)scratch_bytes, l.rows, mbw, l.bytes);
+    SDV_REQUIRE((((uintptr_t)y) & 15) == 0 && (((uintptr_t)cb) & 7) == 0 && (((uintptr_t)cr) & 7) == 0 && (((uintptr_t)scratch) & 7) == 0,
+                "sdv_h264_encode_gops: y must be 16-byte, cb / cr / scratch 8-byte aligned");
+    SDV_REQUIRE((((uintptr_t)ry) & 15) == 0 && (((uintptr_t)rcb) & 7) == 0 && (((uintptr_t)rcr) & 7) == 0,
+                "sdv_h264_encode_gops: ry must be 16-byte, rcb / rcr 8-byte aligned");
+    uint8_t* base = (uint8_t*)scratch;
+    const long long chains = (long long)((n + gop - 1) / gop) * mbh;
+    hipLaunchKernelGGL(h264_gops_kernel, dim3((unsigned)chains), dim3(64), 0, (hipStream_t)stream, y, cb, cr, n, mbh, mbw, qp, gop, first_index, ry, rcb,
+                       rcr, base, l.stride, l.slot, (int32_t*)(base + l.lens_at));
+    SDV_CHECK_LAUNCH("sdv_h264_encode_gops");
     return SDV_OK;
 }
 

@@ -404,3 +404,312 @@ H264_HD void h264_slice_header(Sink& s, unsigned first_mb, unsigned idr_pic_id, 
     h264_put_se(s, qp - 26);                            // slice_qp_delta against pic_init_qp 26
     h264_put_ue(s, 1u);                                 // disable_deblocking_filter_idc
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// GOP path (sdv_hip.h "H.264 P pictures"): IDR pictures coded as above plus P pictures with zero-motion inter prediction, every sample
+// of every macroblock reconstructed.  The macroblock step is cut into per-block pieces (one 4x4 block each: 0..15 luma by
+// luma4x4BlkIdx, 16..19 Cb, 20..23 Cr) that the kernel gives one lane each, and serial pieces that one lane runs; h264_gop_encode_mb
+// runs them all in order on the host.  Nothing above this line is touched by it.
+// ------------------------------------------------------------------------------------------------------------------------------------
+enum { kH264ModeIntra = 0, kH264ModeInter = 1, kH264ModeSkip = 2, kH264ModePcm = 3 };
+enum { kH264GopMax = 256 };
+
+// coded_block_pattern -> codeNum of me(v), inter column of Table 9-4 (ChromaArrayType 1): the inverse of
+// 0 16 1 2 4 8 32 3 5 10 12 15 47 7 11 13 14 6 9 31 35 37 42 44 33 34 36 40 39 43 45 46 17 18 20 24 19 21 26 28 23 27 29 30 22 25 38 41
+H264_HD int h264_cbp_inter_code(int cbp) {
+    const uint8_t t[48] = {0,  2,  3,  7,  4,  8,  17, 13, 5,  18, 9,  14, 10, 15, 16, 11, 1,  32, 33, 36, 34, 37, 44, 40,
+                           35, 45, 38, 41, 39, 42, 43, 19, 6,  24, 25, 20, 26, 21, 46, 28, 27, 47, 22, 29, 23, 30, 31, 12};
+    return t[cbp];
+}
+
+// The state of one macroblock that the pieces share (LDS in the kernel).
+struct __attribute__((aligned(16))) h264_gop_mb {
+    uint8_t sy[256], sc[128];                           // source
+    uint8_t fy[256], fc[128];                           // reference: the co-located samples of the previous reconstruction (P pictures)
+    uint8_t ry[256], rc[128];                           // reconstruction
+    int16_t lev[kH264MbLevels];                         // as above; an inter macroblock keeps 16 levels in each of the blocks 1..16
+    int dcw[24];                                        // transformed DC of every block (Intra16x16 luma, chroma)
+    int dcd[24];                                        // its dequantised DC for the reconstruction
+    int pred_y, pred_c[2][2];                           // the DC predictors
+    int mode;
+};
+
+H264_HD void h264_gop_block_xy(int b, int* x, int* y) {  // sample offset of block b inside its plane of the macroblock
+    if (b < 16) *x = 4 * (2 * ((b >> 2) & 1) + (b & 1)), *y = 4 * (2 * (b >> 3) + ((b >> 1) & 1));
+    else *x = 4 * (b & 1), *y = 4 * ((b >> 1) & 1);
+}
+
+// serial: the DC predictors of the Intra16x16 mode from the chain
+H264_HD void h264_gop_pred(h264_gop_mb* mb, const h264_chain& ch) {
+    mb->pred_y = 128;
+    for (int c = 0; c < 2; ++c) mb->pred_c[c][0] = mb->pred_c[c][1] = 128;
+    if (!ch.have) return;
+    int s = 8;
+    for (int i = 0; i < 16; ++i) s += ch.ycol[i];
+    mb->pred_y = s >> 4;
+    for (int c = 0; c < 2; ++c)
+        for (int h = 0; h < 2; ++h)
+            mb->pred_c[c][h] = (ch.ccol[c][4 * h] + ch.ccol[c][4 * h + 1] + ch.ccol[c][4 * h + 2] + ch.ccol[c][4 * h + 3] + 2) >> 2;
+}
+
+// per luma block: its part of sad_intra and sad_inter
+H264_HD void h264_gop_block_sad(const h264_gop_mb* mb, int b, int* intra, int* inter) {
+    int x, y, si = 0, sp = 0;
+    h264_gop_block_xy(b, &x, &y);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const int s = mb->sy[(y + i) * 16 + x + j], di = s - mb->pred_y, dp = s - (int)mb->fy[(y + i) * 16 + x + j];
+            si += di < 0 ? -di : di, sp += dp < 0 ? -dp : dp;
+        }
+    *intra = si, *inter = sp;
+}
+
+// per block: residual, forward transform, quantisation; returns whether the block has a nonzero level that the cbp looks at (Intra16x16
+// luma and all chroma: AC only; inter luma: all 16)
+H264_HD bool h264_gop_block_forward(h264_gop_mb* mb, int b, bool inter, int qp) {
+    int x, y, xs[16], w[16];
+    h264_gop_block_xy(b, &x, &y);
+    const bool luma = b < 16;
+    const int c = (b - 16) >> 2, stride = luma ? 16 : 8;
+    const uint8_t* src = luma ? mb->sy : mb->sc + c * 64;
+    const uint8_t* ref = luma ? mb->fy : mb->fc + c * 64;
+    const int dc_pred = luma ? mb->pred_y : mb->pred_c[c][y >> 2];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const int at = (y + i) * stride + x + j;
+            xs[i * 4 + j] = (int)src[at] - (inter ? (int)ref[at] : dc_pred);
+        }
+    h264_forward4x4(xs, w);
+    const int q = luma ? qp : h264_qpc(qp), q6 = q % 6, qbits = 15 + q / 6, f = (1 << qbits) / (inter ? 6 : 3);
+    int16_t* lv = mb->lev + (luma ? 1 + b : 19 + (b - 16)) * 16;
+    bool any = false;
+    const bool whole = luma && inter;                   // 16 levels, the DC among them
+    for (int r = whole ? 0 : 1; r < 16; ++r) {
+        const int l = h264_quant(w[r], h264_mf(q6, h264_pos_class(r >> 2, r & 3)), f, qbits);
+        lv[h264_scan_pos(r) - (whole ? 0 : 1)] = (int16_t)l;
+        if (l) any = true;
+    }
+    if (!whole) lv[15] = 0;
+    mb->dcw[b] = w[0];
+    return any;
+}
+
+// serial: the DC blocks (Intra16x16 luma Hadamard; chroma 2x2), their levels and their dequantised values; returns whether a chroma DC
+// level is nonzero
+H264_HD bool h264_gop_dc(h264_gop_mb* mb, bool inter, int qp) {
+    const int q6 = qp % 6, qbits = 15 + qp / 6, f = (1 << qbits) / 3, k = qp / 6, v0 = h264_norm(q6, 0);
+    if (!inter) {
+        int dc[16], hd[16], c4[16], fm[16];
+        for (int b = 0; b < 16; ++b) {
+            int x, y;
+            h264_gop_block_xy(b, &x, &y);
+            dc[y + (x >> 2)] = mb->dcw[b];
+        }
+        h264_hadamard4x4(dc, hd);
+        for (int r = 0; r < 16; ++r) {
+            c4[r] = h264_quant((hd[r] + 1) >> 1, h264_mf(q6, 0), 2 * f, qbits + 1);
+            mb->lev[h264_scan_pos(r)] = (int16_t)c4[r];
+        }
+        h264_hadamard4x4(c4, fm);
+        for (int b = 0; b < 16; ++b) {
+            int x, y;
+            h264_gop_block_xy(b, &x, &y);
+            const int fv = fm[y + (x >> 2)];
+            mb->dcd[b] = k >= 2 ? fv * v0 * (1 << (k - 2)) : (fv * v0 + (1 << (1 - k))) >> (2 - k);
+        }
+    } else {
+        for (int i = 0; i < 16; ++i) mb->lev[i] = 0;
+    }
+    const int qpc = h264_qpc(qp), c6 = qpc % 6, cbits = 15 + qpc / 6, fc = (1 << cbits) / (inter ? 6 : 3), kc = qpc / 6, vc = h264_norm(c6, 0);
+    bool any = false;
+    for (int c = 0; c < 2; ++c) {
+        const int* d2 = mb->dcw + 16 + 4 * c;
+        const int y2[4] = {d2[0] + d2[1] + d2[2] + d2[3], d2[0] - d2[1] + d2[2] - d2[3], d2[0] + d2[1] - d2[2] - d2[3], d2[0] - d2[1] - d2[2] + d2[3]};
+        int d[4];
+        for (int i = 0; i < 4; ++i) {
+            d[i] = h264_quant(y2[i], h264_mf(c6, 0), 2 * fc, cbits + 1);
+            mb->lev[(17 + c) * 16 + i] = (int16_t)d[i];
+            if (d[i]) any = true;
+        }
+        for (int i = 4; i < 16; ++i) mb->lev[(17 + c) * 16 + i] = 0;
+        const int f2[4] = {d[0] + d[1] + d[2] + d[3], d[0] - d[1] + d[2] - d[3], d[0] + d[1] - d[2] - d[3], d[0] - d[1] - d[2] + d[3]};
+        for (int i = 0; i < 4; ++i) mb->dcd[16 + 4 * c + i] = (f2[i] * vc * (1 << kc)) >> 1;
+    }
+    return any;
+}
+
+// macroblock_layer() of an Intra16x16 macroblock, mb_type offset 0 in an I slice, 5 in a P slice
+template <class Sink>
+H264_HD void h264_gop_code_intra(const int16_t* lev, int cbp_luma, int cbp_chroma, const h264_chain& left, int type_offset, Sink& s, uint8_t* tcy,
+                                 uint8_t* tcc) {
+    h264_put_ue(s, (unsigned)(type_offset + 1 + 2 + 4 * cbp_chroma + (cbp_luma ? 12 : 0)));
+    h264_put_ue(s, 0u);                                 // intra_chroma_pred_mode: DC
+    h264_put_se(s, 0);                                  // mb_qp_delta
+    h264_code_block(lev, 16, h264_nc(left.have ? left.tcy[0] : -1, -1), s);
+    if (cbp_luma)
+        for (int b = 0; b < 16; ++b) {
+            const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+            const int a = bx ? tcy[by * 4 + bx - 1] : left.have ? left.tcy[by] : -1;
+            const int t = by ? tcy[(by - 1) * 4 + bx] : -1;
+            tcy[by * 4 + bx] = (uint8_t)h264_code_block(lev + (1 + b) * 16, 15, h264_nc(a, t), s);
+        }
+}
+// macroblock_layer() of a P_L0_16x16 macroblock (cbp != 0) up to and including the luma residual
+template <class Sink>
+H264_HD void h264_gop_code_inter(const int16_t* lev, int cbp_luma, int cbp_chroma, const h264_chain& left, Sink& s, uint8_t* tcy) {
+    h264_put_ue(s, 0u);                                 // mb_type P_L0_16x16 (ref_idx_l0 is not sent: one active reference)
+    h264_put_se(s, 0), h264_put_se(s, 0);               // mvd_l0
+    h264_put_ue(s, (unsigned)h264_cbp_inter_code(cbp_luma + 16 * cbp_chroma));
+    h264_put_se(s, 0);                                  // mb_qp_delta
+    for (int b = 0; b < 16; ++b) {
+        if (!((cbp_luma >> (b >> 2)) & 1)) continue;
+        const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+        const int a = bx ? tcy[by * 4 + bx - 1] : left.have ? left.tcy[by] : -1;
+        const int t = by ? tcy[(by - 1) * 4 + bx] : -1;
+        tcy[by * 4 + bx] = (uint8_t)h264_code_block(lev + (1 + b) * 16, 16, h264_nc(a, t), s);
+    }
+}
+// the chroma residual of either
+template <class Sink>
+H264_HD void h264_gop_code_chroma(const int16_t* lev, int cbp_chroma, const h264_chain& left, Sink& s, uint8_t* tcc) {
+    if (cbp_chroma)
+        for (int c = 0; c < 2; ++c) h264_code_block(lev + (17 + c) * 16, 4, -1, s);
+    if (cbp_chroma == 2)
+        for (int c = 0; c < 2; ++c)
+            for (int b = 0; b < 4; ++b) {
+                const int bx = b & 1, by = b >> 1;
+                const int a = bx ? tcc[c * 4 + by * 2] : left.have ? left.tcc[c][by] : -1;
+                const int t = by ? tcc[c * 4 + bx] : -1;
+                tcc[c * 4 + b] = (uint8_t)h264_code_block(lev + (19 + c * 4 + b) * 16, 15, h264_nc(a, t), s);
+            }
+}
+template <class Sink>
+H264_HD void h264_gop_code_mb(const int16_t* lev, bool inter, bool p_slice, int cbp_luma, int cbp_chroma, const h264_chain& left, Sink& s,
+                              uint8_t* tcy, uint8_t* tcc) {
+    for (int i = 0; i < 16; ++i) tcy[i] = 0;            // [by * 4 + bx]
+    for (int i = 0; i < 8; ++i) tcc[i] = 0;             // [c * 4 + by * 2 + bx]
+    if (inter) h264_gop_code_inter(lev, cbp_luma, cbp_chroma, left, s, tcy);
+    else h264_gop_code_intra(lev, cbp_luma, cbp_chroma, left, p_slice ? 5 : 0, s, tcy, tcc);
+    h264_gop_code_chroma(lev, cbp_chroma, left, s, tcc);
+}
+
+// serial: mode decision after the levels are known (nz: bit b set when h264_gop_block_forward returned true for block b), the counting
+// pass, the I_PCM decision, the bits; leaves mb->mode and the chain's TotalCoeffs.  skip_run: the P_Skip macroblocks not yet written.
+H264_HD void h264_gop_serial(h264_gop_mb* mb, unsigned nz, bool any_cdc, bool inter, bool p_slice, h264_chain& ch, h264_writer& w, int* skip_run) {
+    int cbp_luma = 0;
+    if (inter) {
+        for (int i = 0; i < 4; ++i)
+            if (nz & (0xfu << (4 * i))) cbp_luma |= 1 << i;
+    } else if (nz & 0xffffu) {
+        cbp_luma = 15;
+    }
+    const int cbp_chroma = (nz & 0xff0000u) ? 2 : any_cdc ? 1 : 0;
+    if (inter && !cbp_luma && !cbp_chroma) {            // P_Skip: inferred vector (0, 0), no residual
+        ++*skip_run;
+        mb->mode = kH264ModeSkip;
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 0;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 0;
+        return;
+    }
+    if (p_slice) {
+        h264_put_ue(w, (unsigned)*skip_run);            // mb_skip_run
+        *skip_run = 0;
+    }
+    uint8_t tcy[16], tcc[8];
+    h264_counter cnt;
+    cnt.bits = 0, cnt.failed = false;
+    h264_gop_code_mb(mb->lev, inter, p_slice, cbp_luma, cbp_chroma, ch, cnt, tcy, tcc);
+    if (cnt.failed || cnt.bits > 3200) {                // Annex A.3.1 / level_prefix <= 15: I_PCM
+        h264_put_ue(w, p_slice ? 30u : 25u);
+        while (w.n) w.put(0u, 1);                       // pcm_alignment_zero_bit
+        for (int i = 0; i < 256; ++i) w.put(mb->sy[i], 8);
+        for (int i = 0; i < 128; ++i) w.put(mb->sc[i], 8);
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 16;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 16;
+        mb->mode = kH264ModePcm;
+        return;
+    }
+    h264_gop_code_mb(mb->lev, inter, p_slice, cbp_luma, cbp_chroma, ch, w, tcy, tcc);
+    for (int i = 0; i < 4; ++i) ch.tcy[i] = tcy[i * 4 + 3];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 2; ++i) ch.tcc[c][i] = tcc[c * 4 + i * 2 + 1];
+    mb->mode = inter ? kH264ModeInter : kH264ModeIntra;
+}
+
+// per block: reconstruction (8.5) by the macroblock's mode
+H264_HD void h264_gop_block_recon(h264_gop_mb* mb, int b, int qp) {
+    int x, y;
+    h264_gop_block_xy(b, &x, &y);
+    const bool luma = b < 16;
+    const int c = (b - 16) >> 2, stride = luma ? 16 : 8;
+    const uint8_t* src = luma ? mb->sy : mb->sc + c * 64;
+    const uint8_t* ref = luma ? mb->fy : mb->fc + c * 64;
+    uint8_t* rec = luma ? mb->ry : mb->rc + c * 64;
+    const int mode = mb->mode;
+    if (mode == kH264ModePcm || mode == kH264ModeSkip) {
+        const uint8_t* from = mode == kH264ModePcm ? src : ref;
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) rec[(y + i) * stride + x + j] = from[(y + i) * stride + x + j];
+        return;
+    }
+    const bool inter = mode == kH264ModeInter, whole = luma && inter;
+    const int q = luma ? qp : h264_qpc(qp), q6 = q % 6, k = q / 6;
+    const int16_t* lv = mb->lev + (luma ? 1 + b : 19 + (b - 16)) * 16;
+    int d[16], r[16];
+    for (int p = whole ? 0 : 1; p < 16; ++p) {
+        const int ras = h264_zigzag(p);
+        d[ras] = (int)lv[p - (whole ? 0 : 1)] * h264_norm(q6, h264_pos_class(ras >> 2, ras & 3)) * (1 << k);
+    }
+    if (!whole) d[0] = mb->dcd[b];
+    h264_inverse4x4(d, r);
+    const int dc_pred = luma ? mb->pred_y : mb->pred_c[c][y >> 2];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const int at = (y + i) * stride + x + j;
+            rec[at] = (uint8_t)h264_clip255((inter ? (int)ref[at] : dc_pred) + r[i * 4 + j]);
+        }
+}
+
+// serial: what the right neighbour reads of the reconstruction
+H264_HD void h264_gop_chain(const h264_gop_mb* mb, h264_chain& ch) {
+    for (int i = 0; i < 16; ++i) ch.ycol[i] = mb->ry[i * 16 + 15];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 8; ++i) ch.ccol[c][i] = mb->rc[c * 64 + i * 8 + 7];
+    ch.have = 1;
+}
+
+// P slice header (7.3.3): frame_num u(4), no override, no list modification, sliding-window marking
+template <class Sink>
+H264_HD void h264_p_slice_header(Sink& s, unsigned first_mb, unsigned frame_num, int qp) {
+    h264_put_ue(s, first_mb);
+    h264_put_ue(s, 5u);                                 // slice_type: P, and every slice of the picture is
+    h264_put_ue(s, 0u);                                 // pic_parameter_set_id
+    s.put(frame_num & 15u, 4);
+    s.put(0u, 3);                                       // num_ref_idx_active_override_flag, ref_pic_list_modification_flag_l0,
+                                                        // adaptive_ref_pic_marking_mode_flag
+    h264_put_se(s, qp - 26);
+    h264_put_ue(s, 1u);                                 // disable_deblocking_filter_idc
+}
+
+// The whole macroblock step in order, one piece after the other (host; the kernel spreads the per-block pieces over its lanes).
+// mb->sy / sc (and fy / fc in a P picture) are loaded; leaves mb->ry / rc.
+inline void h264_gop_encode_mb(h264_gop_mb* mb, h264_chain& ch, bool p_slice, int qp, h264_writer& w, int* skip_run) {
+    h264_gop_pred(mb, ch);
+    bool inter = false;
+    if (p_slice) {
+        int si = 0, sp = 0;
+        for (int b = 0; b < 16; ++b) {
+            int a, c;
+            h264_gop_block_sad(mb, b, &a, &c);
+            si += a, sp += c;
+        }
+        inter = !(si < sp);
+    }
+    unsigned nz = 0;
+    for (int b = 0; b < 24; ++b)
+        if (h264_gop_block_forward(mb, b, inter, qp)) nz |= 1u << b;
+    const bool any_cdc = h264_gop_dc(mb, inter, qp);
+    h264_gop_serial(mb, nz, any_cdc, inter, p_slice, ch, w, skip_run);
+    for (int b = 0; b < 24; ++b) h264_gop_block_recon(mb, b, qp);
+    h264_gop_chain(mb, ch);
+}

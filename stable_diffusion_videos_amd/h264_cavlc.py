@@ -7,6 +7,10 @@ one IDR slice per macroblock row so that every row is an independent bit stream 
 would break the 3200-bit limit of Annex A.3.1.  The stream rule is written down in include/sdv_hip.h and DESIGN.md ("H.264 CAVLC intra
 encoder"); tests/h264_ref.py restates it and decodes it.
 
+``gop`` > 1 (opt-in on top of the opt-in; sdv_hip.h and DESIGN.md "H.264 P pictures") makes picture k of a call an IDR picture only when
+``k % gop == 0`` and a P picture otherwise: zero-motion inter prediction from the reconstruction of the picture before it, ``P_Skip``
+where nothing is left to code.  tests/h264_p_ref.py restates and decodes that stream.  ``gop`` 1 is the code and the bytes described above.
+
 Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
 """
 from __future__ import annotations
@@ -18,6 +22,7 @@ import torch
 from . import hip
 
 DEFAULT_QP = 16
+DEFAULT_GOP = 1                                                                                 # a setting, not a measured optimum
 
 
 def check_qp(qp) -> int:
@@ -26,16 +31,27 @@ def check_qp(qp) -> int:
     return qp
 
 
+def check_gop(gop) -> int:
+    if isinstance(gop, bool) or not isinstance(gop, int) or not 1 <= gop <= hip.H264_GOP_MAX:
+        raise ValueError(f"h264 gop must be an integer in 1 .. {hip.H264_GOP_MAX}, got {gop!r}")
+    return gop
+
+
 class H264Encoder:
     """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
-    (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.
+    (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.  With ``gop``
+    > 1 only the pictures at positions ``k % gop == 0`` of a call are IDR pictures (``last_sync`` lists them after every call); the
+    others are P pictures, and every call starts a new GOP.  ``return_recon=True`` returns ``(samples, (ry, rcb, rcr))``, the
+    decoder's pictures as padded planes in GPU memory (they belong to the workspace: the next call overwrites them).
 
     Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
     prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
     capacity bound of sdv_hip.h, so no batch can fail to fit."""
 
-    def __init__(self, qp: int = DEFAULT_QP, device=None):
+    def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP):
         self.qp = check_qp(qp)
+        self.gop = check_gop(gop)
+        self.last_sync: List[int] = []
         self.device = torch.device(device) if device is not None else None
         self._ws: Dict[tuple, dict] = {}
         self.last_bytes_to_host = 0
@@ -44,15 +60,19 @@ class H264Encoder:
         key = (n, mbh, mbw, str(device))
         ws = self._ws.get(key)
         if ws is None:
-            cap = hip.h264_out_bytes(n, mbh, mbw)
+            gops = self.gop > 1
+            cap = hip.h264_gop_out_bytes(n, mbh, mbw) if gops else hip.h264_out_bytes(n, mbh, mbw)
+            scratch = hip.h264_gop_scratch_bytes(n, mbh, mbw) if gops else hip.h264_scratch_bytes(n, mbh, mbw)
             ws = dict(y=torch.empty((n, 16 * mbh, 16 * mbw), dtype=torch.uint8, device=device),
                       cb=torch.empty((n, 8 * mbh, 8 * mbw), dtype=torch.uint8, device=device),
                       cr=torch.empty((n, 8 * mbh, 8 * mbw), dtype=torch.uint8, device=device),
-                      scratch=torch.empty((hip.h264_scratch_bytes(n, mbh, mbw),), dtype=torch.uint8, device=device),
+                      scratch=torch.empty((scratch,), dtype=torch.uint8, device=device),
                       out=torch.empty((cap,), dtype=torch.uint8, device=device),
                       offsets=torch.zeros((n + 1,), dtype=torch.int64, device=device),
                       offsets_host=torch.empty((n + 1,), dtype=torch.int64, pin_memory=True),
                       out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True))
+            if gops:                                                                            # the reference pictures stay in HBM
+                ws.update(ry=torch.empty_like(ws["y"]), rcb=torch.empty_like(ws["cb"]), rcr=torch.empty_like(ws["cr"]))
             if len(self._ws) >= 4:                                                              # a walk uses one or two shapes
                 self._ws.pop(next(iter(self._ws)))
             self._ws[key] = ws
@@ -65,23 +85,24 @@ class H264Encoder:
         if self.device is not None and self.device.index is not None and t.device != self.device:
             raise hip.SdvHipError(f"H264Encoder.{what}: frames are on {t.device}, the encoder was made for {self.device}")
 
-    def encode(self, frames_u8: torch.Tensor, first_index: int = 0) -> List[bytes]:
+    def encode(self, frames_u8: torch.Tensor, first_index: int = 0, return_recon: bool = False):
         self._check_device("encode", frames_u8)
         if frames_u8.dtype != torch.uint8 or frames_u8.ndim != 4 or frames_u8.shape[-1] != 3:
             raise hip.SdvHipError(f"H264Encoder.encode: expected a uint8 [n, H, W, 3] tensor, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
         frames_u8 = frames_u8.contiguous()
         n, H, W, _ = frames_u8.shape
         if n == 0:
-            return []
+            self.last_sync = []
+            return ([], None) if return_recon else []
         if H % 2 or W % 2 or not (2 <= H <= hip.H264_MAX_DIM and 2 <= W <= hip.H264_MAX_DIM):
             raise hip.SdvHipError(f"H264Encoder.encode: frame size must be even and 2 .. {hip.H264_MAX_DIM}, got {H} x {W}")
         mbh, mbw = hip.h264_mb_grid(H, W)
         with torch.cuda.device(frames_u8.device):
             ws = self._workspace(n, mbh, mbw, frames_u8.device)
             hip.h264_planes(frames_u8, ws["y"], ws["cb"], ws["cr"])
-            return self._rows_and_pack(ws, n, mbh, mbw, first_index)
+            return self._rows_and_pack(ws, n, mbh, mbw, first_index, return_recon)
 
-    def encode_planes(self, y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, first_index: int = 0) -> List[bytes]:
+    def encode_planes(self, y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, first_index: int = 0, return_recon: bool = False):
         """The same from padded planes ``y [n, 16 mbh, 16 mbw]``, ``cb`` / ``cr [n, 8 mbh, 8 mbw]`` (any sample values)."""
         for t in (y, cb, cr):
             self._check_device("encode_planes", t)
@@ -90,11 +111,18 @@ class H264Encoder:
         n, mbh, mbw = y.shape[0], y.shape[1] // 16, y.shape[2] // 16
         with torch.cuda.device(y.device):
             ws = dict(self._workspace(n, mbh, mbw, y.device), y=y.contiguous(), cb=cb.contiguous(), cr=cr.contiguous())
-            return self._rows_and_pack(ws, n, mbh, mbw, first_index)
+            return self._rows_and_pack(ws, n, mbh, mbw, first_index, return_recon)
 
-    def _rows_and_pack(self, ws: dict, n: int, mbh: int, mbw: int, first_index: int) -> List[bytes]:
-        hip.h264_encode_rows(ws["y"], ws["cb"], ws["cr"], self.qp, int(first_index), ws["scratch"])
-        hip.h264_pack(ws["scratch"], n, mbh, mbw, ws["out"], ws["offsets"])
+    def _rows_and_pack(self, ws: dict, n: int, mbh: int, mbw: int, first_index: int, return_recon: bool = False):
+        if self.gop == 1:
+            if return_recon:
+                raise hip.SdvHipError("H264Encoder: the all-intra path (gop 1) reconstructs only what its chains read; return_recon needs gop > 1")
+            hip.h264_encode_rows(ws["y"], ws["cb"], ws["cr"], self.qp, int(first_index), ws["scratch"])
+            hip.h264_pack(ws["scratch"], n, mbh, mbw, ws["out"], ws["offsets"])
+        else:
+            hip.h264_encode_gops(ws["y"], ws["cb"], ws["cr"], self.qp, self.gop, int(first_index), ws["ry"], ws["rcb"], ws["rcr"], ws["scratch"])
+            hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
+        self.last_sync = list(range(0, n, self.gop))
         ws["offsets_host"].copy_(ws["offsets"], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         offs = ws["offsets_host"].tolist()
@@ -103,15 +131,16 @@ class H264Encoder:
         torch.cuda.current_stream().synchronize()
         payload = ws["out_host"].numpy()
         self.last_bytes_to_host = used + 8 * (n + 1)
-        return [payload[offs[k]:offs[k + 1]].tobytes() for k in range(n)]
+        samples = [payload[offs[k]:offs[k + 1]].tobytes() for k in range(n)]
+        return (samples, (ws["ry"], ws["rcb"], ws["rcr"])) if return_recon else samples
 
 
 _encoders: Dict[tuple, H264Encoder] = {}
 
 
-def encoder_for(qp: int, device) -> H264Encoder:
-    """One cached encoder (and its workspaces) per quality setting and device."""
-    key = (check_qp(qp), str(device))
+def encoder_for(qp: int, device, gop: int = DEFAULT_GOP) -> H264Encoder:
+    """One cached encoder (and its workspaces) per quality setting, GOP length and device."""
+    key = (check_qp(qp), str(device), check_gop(gop))
     if key not in _encoders:
-        _encoders[key] = H264Encoder(qp, device)
+        _encoders[key] = H264Encoder(qp, device, gop)
     return _encoders[key]

@@ -105,6 +105,7 @@ _SIGNATURES = {
     "sdv_png_crc32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sdv_h264_planes_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 4),
     "sdv_h264_encode_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "sdv_h264_encode_gops": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
     "sdv_h264_pack": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sdv_h264_vlc_tables": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32]),
 }
@@ -1531,6 +1532,62 @@ def h264_encode_rows(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: in
     """Code every macroblock row of every picture as one IDR slice into its slot of ``scratch`` (``h264_scratch_bytes``), by the stream
     rule of sdv_hip.h (``torch.ops.sdv.k_h264_encode_rows`` -> sdv_h264_encode_rows).  Picture k carries idr_pic_id (first_index + k) & 1."""
     _k_h264_encode_rows(y, cb, cr, int(qp), int(first_index), scratch)
+
+
+H264_GOP_MAX = 256
+H264_GOP_MAX_MBW = 1008
+
+
+def h264_gop_slot_mbw(mbw: int) -> int:
+    """The GOP path keeps a slice in the slot of a picture this many macroblocks wide (sdv_hip.h "Capacity of the GOP path"): a P slice
+    carries an mb_skip_run per macroblock on top of the 3200 bits, and its header is not bounded by 8 bytes."""
+    return int(mbw) + 1 + int(mbw) // 64
+
+
+def h264_gop_out_bytes(n: int, mbh: int, mbw: int) -> int:
+    """The capacity sdv_h264_pack demands of ``out`` behind ``h264_encode_gops``."""
+    return h264_out_bytes(n, mbh, h264_gop_slot_mbw(mbw))
+
+
+def h264_gop_scratch_bytes(n: int, mbh: int, mbw: int) -> int:
+    return h264_scratch_bytes(n, mbh, h264_gop_slot_mbw(mbw))
+
+
+def _h264_encode_gops_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch):
+    what = "h264_encode_gops"
+    n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    if mbw > H264_GOP_MAX_MBW:
+        raise SdvHipError(f"{what}: pictures wider than {H264_GOP_MAX_MBW} macroblocks are not coded with P pictures, got mbw={mbw}")
+    if first_index < 0:
+        raise SdvHipError(f"{what}: first_index must be >= 0, got {first_index}")
+    _h264_u8(what, "ry", ry, y.shape)
+    _h264_u8(what, "rcb", rcb, cb.shape)
+    _h264_u8(what, "rcr", rcr, cr.shape)
+    _h264_u8(what, "scratch", scratch)
+    need = h264_gop_scratch_bytes(n, mbh, mbw)
+    if scratch.ndim != 1 or scratch.numel() < need:
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n * mbh} slices of {mbw} macroblocks need {need}")
+    lib = load()
+    args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(first_index) & 0x7fffffff,
+            _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"), _ptr(scratch, name="scratch"), scratch.numel())
+    _launch("h264_encode_gops", dict(bytes=3.0 * y.numel()), lambda: _check(lib.sdv_h264_encode_gops(*args, _stream()), "sdv_h264_encode_gops"))
+
+
+_k_h264_encode_gops = _defop("k_h264_encode_gops(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int first_index, Tensor(a!) ry, Tensor(b!) rcb, "
+                             "Tensor(c!) rcr, Tensor(d!) scratch) -> ()", _h264_encode_gops_impl)
+
+
+def h264_encode_gops(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, first_index: int, ry: torch.Tensor,
+                     rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor):
+    """Code the pictures in groups of ``gop``: picture k an IDR picture when ``k % gop == 0``, else a P picture predicted (zero motion)
+    from the reconstruction of picture k - 1, by the stream rule of sdv_hip.h (``torch.ops.sdv.k_h264_encode_gops`` ->
+    sdv_h264_encode_gops).  Slices go to the slots of ``scratch`` (``h264_gop_scratch_bytes``; pack with ``h264_gop_slot_mbw(mbw)``), the
+    reconstruction of every picture to ``ry`` / ``rcb`` / ``rcr``."""
+    _k_h264_encode_gops(y, cb, cr, int(qp), int(gop), int(first_index), ry, rcb, rcr, scratch)
 
 
 def _h264_pack_impl(scratch, n, mbh, mbw, out, offsets):

@@ -121,6 +121,7 @@ class StableDiffusionWalkPipeline:
         self.png_matches = False           # the HIP PNG encoder's LZ77 matches and GPU-side CRC-32 (smaller files, more kernel time); SDV_PNG_MATCHES wins
         self.video_codec = None            # the dependency-free mp4 writer's codec: None = video.py's default, "h264" / "mjpeg" / "h264-cavlc"; SDV_VIDEO_CODEC wins
         self.h264_qp = 16                  # quantiser of the "h264-cavlc" track (0 .. 51; h264_cavlc.py); SDV_H264_QP wins
+        self.h264_gop = 1                  # pictures per IDR picture of the "h264-cavlc" track (1 .. 256; 1 = all intra); SDV_H264_GOP wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
@@ -658,6 +659,20 @@ class StableDiffusionWalkPipeline:
             raise ValueError(f"SDV_H264_QP / h264_qp must be an integer 0 .. 51, got {qp!r}")
         return qp
 
+    def h264_gop_choice(self) -> int:
+        """The GOP length of the ``h264-cavlc`` video track: the environment variable SDV_H264_GOP (an integer 1 .. 256) when it is set,
+        else ``self.h264_gop``.  1 = every picture an IDR picture; a setting, not a measured optimum."""
+        env = os.environ.get("SDV_H264_GOP")
+        if env is None or env == "":
+            gop = self.h264_gop
+        elif env.isdigit():
+            gop = int(env)
+        else:
+            raise ValueError(f"SDV_H264_GOP must be an integer 1 .. 256, got {env!r}")
+        if isinstance(gop, bool) or not isinstance(gop, int) or not 1 <= gop <= 256:
+            raise ValueError(f"SDV_H264_GOP / h264_gop must be an integer 1 .. 256, got {gop!r}")
+        return gop
+
     def make_clip_frames(self, prompt_a: str, prompt_b: str, seed_a: int, seed_b: int, num_interpolation_steps: int = 5,
                          save_path: Union[str, Path] = "outputs/", num_inference_steps: int = 50,
                          guidance_scale: float = 7.5, eta: float = 0.0, height: Optional[int] = None,
@@ -889,11 +904,11 @@ class StableDiffusionWalkPipeline:
                 make_video_pyav(c["save_path"], audio_filepath=audio_filepath, fps=fps, output_filepath=c["mp4"],
                                 glob_pattern=f"*{image_file_ext}", audio_offset=audio_offset,
                                 audio_duration=num_step / fps, sr=44100, codec=self.video_codec,
-                                h264_qp=self.h264_qp_choice())                                  # :787-796
+                                h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice())  # :787-796
             result = make_video_pyav(save_path_root, audio_filepath=audio_filepath, fps=fps, audio_offset=audio_start_sec,
                                      audio_duration=sum(num_interpolation_steps) / fps, output_filepath=output_filepath,
                                      glob_pattern=f"**/*{image_file_ext}", sr=44100, codec=self.video_codec,
-                                     h264_qp=self.h264_qp_choice())                              # :798-807
+                                     h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice())   # :798-807
         if world_size > 1:
             parallel.barrier()
             result = str(output_filepath) if result is None else result

@@ -12,7 +12,9 @@ they are not, a dependency-free writer produces a standards-conforming ISO-BMFF 
 so that ``walk()`` returns the same ``{name}.mp4`` paths as the reference, in the reference's video codec and pixel format, and
 the music video still carries its music; entropy-coded H.264 and AAC need ffmpeg and are what this mode lacks by default.  Opt-in,
 ``SDV_VIDEO_CODEC=h264-cavlc`` (or ``codec="h264-cavlc"``) writes an entropy-coded all-intra H.264 track compressed on the GPU
-(h264_cavlc.py, csrc/sdv_h264.hip) in the same ``avc1`` container.  Frames are read once each (the reference's pairwise ``torch.cat``
+(h264_cavlc.py, csrc/sdv_h264.hip) in the same ``avc1`` container; ``h264_gop`` > 1 (the pipeline: ``pipe.h264_gop``,
+``SDV_H264_GOP``) adds P pictures to it (an IDR picture every ``gop`` pictures of an upload batch, an ``stss`` box naming them).
+Frames are read once each (the reference's pairwise ``torch.cat``
 is O(n^2), :91-93).
 """
 from __future__ import annotations
@@ -35,6 +37,7 @@ DEFAULT_CODEC = "h264"
 # The I_PCM H.264 track is UNCOMPRESSED (1.5 bytes per pixel: 0.39 MB per 512 x 512 frame, 6.3 MB per upsampled 2048 x 2048 frame,
 # several times what libx264 crf 10 writes): above this many bytes of video the dependency-free writer falls back to Motion-JPEG
 # unless SDV_VIDEO_CODEC asks for h264 explicitly (long or upsampled walks produced multi-GB mp4 files).
+H264_BATCH_BYTES = 64 << 20            # raw frames per upload / encode batch of the "h264-cavlc" track
 H264_PCM_MAX_BYTES = int(os.environ.get("SDV_H264_PCM_MAX_BYTES", str(1 << 30)))
 
 
@@ -89,11 +92,13 @@ def _pcm_samples(frames, width: int, height: int):
 
 
 def write_h264_mp4(frames, width: int, height: int, fps: float, path: Union[str, Path],
-                   audio: Optional[np.ndarray] = None, sr: int = 44100, samples=None) -> str:
+                   audio: Optional[np.ndarray] = None, sr: int = 44100, samples=None, sync_samples=None) -> str:
     """ISO base media file with an H.264 video track (sample entry ``avc1`` + ``avcC``; every sample one IDR picture of I_PCM
     macroblocks, h264.py) and the optional PCM audio track: ftyp | mdat (64-bit size; length-prefixed NAL units streamed to disk
     frame by frame, then the PCM samples) | moov.  ``frames``: iterable of uint8 RGB [H, W, 3].  ``samples``: an iterable of ready-made
-    samples (each the length-prefixed NAL units of one picture, coded against ``h264.sps_pps``; h264_cavlc.py) instead of ``frames``."""
+    samples (each the length-prefixed NAL units of one picture, coded against ``h264.sps_pps``; h264_cavlc.py) instead of ``frames``.
+    ``sync_samples``: the 0-based positions of the IDR pictures (a list, read after ``samples`` is exhausted, so a generator may fill
+    it); an ``stss`` box is written only when it is given and does not name every sample."""
     from . import h264
     timescale = 90000
     delta = int(round(timescale / float(fps)))
@@ -129,8 +134,13 @@ def write_h264_mp4(frames, width: int, height: int, fps: float, path: Union[str,
         stsc = _full(b"stsc", 0, 0, struct.pack(">IIII", 1, 1, n, 1))
         stsz = _full(b"stsz", 0, 0, struct.pack(">II", 0, n) + struct.pack(f">{n}I", *sizes))
         stco = _full(b"stco", 0, 0, struct.pack(">II", 1, data_offset))
-        # no stss box: every sample is a sync sample (all pictures are IDR pictures)
-        stbl = _box(b"stbl", stsd + stts + stsc + stsz + stco)
+        # no stss box: every sample is a sync sample (all pictures are IDR pictures) ...
+        stss = b""
+        if sync_samples is not None and sorted(set(sync_samples)) != list(range(n)):             # ... unless the track has P pictures
+            sync = sorted(set(int(k) for k in sync_samples))
+            assert sync and sync[0] == 0 and sync[-1] < n, "the first sample of a track is a sync sample"
+            stss = _full(b"stss", 0, 0, struct.pack(f">I{len(sync)}I", len(sync), *(k + 1 for k in sync)))
+        stbl = _box(b"stbl", stsd + stts + stss + stsc + stsz + stco)
         traks = _box(b"trak", tkhd + _box(b"mdia", mdhd + hdlr + _box(b"minf", vmhd + dinf + stbl)))
         if n_audio:
             traks += _pcm_audio_trak(n_audio, sr, a_duration, data_offset + video_bytes, matrix, dinf)
@@ -215,10 +225,11 @@ LAST_CODEC: dict = {}
 def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./images", audio_filepath=None, fps: int = 30,
                     audio_offset: int = 0, audio_duration: int = 2, sr: int = 22050,
                     output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png", codec: Optional[str] = None,
-                    h264_qp: Optional[int] = None):
+                    h264_qp: Optional[int] = None, h264_gop: Optional[int] = None):
     """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it.  ``codec``: what
     ``SDV_VIDEO_CODEC`` selects (the variable wins): ``"h264"`` (I_PCM), ``"mjpeg"`` or ``"h264-cavlc"`` - the entropy-coded intra
-    stream of h264_cavlc.py at quantiser ``h264_qp`` (0 .. 51, default 16), compressed in GPU memory."""
+    stream of h264_cavlc.py at quantiser ``h264_qp`` (0 .. 51, default 16), compressed in GPU memory; ``h264_gop``
+    (1 .. 256, default 1) > 1 codes only every ``h264_gop``-th picture as an IDR picture and the others as P pictures."""
     output_filepath = str(output_filepath)
     gpu_frames = None                      # a uint8 tensor in GPU memory: a Motion-JPEG track is compressed there (jpeg.py)
     if isinstance(frames_or_frame_dir, torch.Tensor) and frames_or_frame_dir.is_cuda and frames_or_frame_dir.dtype == torch.uint8 \
@@ -257,7 +268,9 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     cavlc_device = None
     if codec == "h264-cavlc":
         from .h264_cavlc import DEFAULT_QP, check_qp
+        from .h264_cavlc import DEFAULT_GOP, check_gop
         qp = check_qp(DEFAULT_QP if h264_qp is None else h264_qp)
+        gop = check_gop(DEFAULT_GOP if h264_gop is None else h264_gop)
         if h % 2 or w % 2:
             codec = "h264"                                                                     # (the odd-size rule below sends it to Motion-JPEG)
         elif gpu_frames is not None:
@@ -289,10 +302,14 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     LAST_CODEC.clear()
     LAST_CODEC.update(path=output_filepath, video={"h264": "h264 (I_PCM)", "h264-cavlc": "h264 (CAVLC intra)"}.get(codec, "mjpeg"),
                       audio="pcm_s16le" if audio is not None else None, why=why)
+    if codec == "h264-cavlc" and gop > 1:
+        LAST_CODEC["video"] = f"h264 (CAVLC, gop {gop})"
     if codec == "h264-cavlc":
         from .h264_cavlc import encoder_for as h264_encoder_for
-        enc = h264_encoder_for(qp, cavlc_device)
-        step = max(1, (64 << 20) // (h * w * 3))                                            # batches of about 64 MB of raw frames
+        enc = h264_encoder_for(qp, cavlc_device, gop)
+        step = max(1, H264_BATCH_BYTES // (h * w * 3))                                      # batches of about 64 MB of raw frames
+        step = max(gop, step // gop * gop)                                                  # whole GOPs: the file does not depend on it
+        sync: Optional[List[int]] = [] if gop > 1 else None
 
         def cavlc_samples():
             for k in range(0, n_frames, step):
@@ -302,8 +319,10 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
                     batch = torch.from_numpy(np.stack([np.ascontiguousarray(fr[..., :3]) for fr in frames[k:k + step]])).to(cavlc_device)
                 assert tuple(batch.shape[1:3]) == (h, w), "all frames of a video have one size"
                 yield from enc.encode(batch.contiguous(), first_index=k)
+                if sync is not None:
+                    sync.extend(k + j for j in enc.last_sync)
 
-        return write_h264_mp4(None, w, h, fps, output_filepath, audio=audio, sr=sr, samples=cavlc_samples())
+        return write_h264_mp4(None, w, h, fps, output_filepath, audio=audio, sr=sr, samples=cavlc_samples(), sync_samples=sync)
     if codec == "h264":
         return write_h264_mp4(frames if frames is not None else _frames_uint8(frames_or_frame_dir, glob_pattern), w, h, fps, output_filepath,
                               audio=audio, sr=sr)

@@ -1,6 +1,6 @@
 """GPU H.264 CAVLC intra encoder (h264_cavlc.H264Encoder) against the two video tracks it can stand in for, on the same box.
 
-    python tools/h264_bench.py [--out FILE] [--reps 5]
+    python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N]
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -12,6 +12,11 @@ noise (the worst case).  Per case:
   * bytes per frame at qp 10 / 16 / 22 against I_PCM and Motion-JPEG q95;
   * at 512 x 512, Y-PSNR of the reconstruction at qp 10 / 16 / 22: the first frame's sample decoded by the decoder of
     tests/h264_ref.py against the integer-rule Y' of the source.
+With ``--gop N`` (N > 1) the tool measures the GOP path instead (P pictures, h264_cavlc.H264Encoder(gop=N)): per frame set one row for
+gop 1 - the all-intra code, the comparison - and one for gop N, side by side: encode() ms and frames/s with warm workspaces, bytes per
+frame, and Y-PSNR of the reconstruction of all frames (the planes sdv_h264_encode_gops leaves in HBM; at gop 1 that entry point writes
+the intra stream's bytes).  Frame sets: the tiny pipeline's frames, and the temporal kinds ``fade`` (lerp between two glyph frames) and
+``pan`` (a glyph frame shifted by k pixels in picture k) of tests/h264_p_ref.py, at 128 x 512 x 512 and 8 x 2048 x 2048.
 There is no fallback: without a GPU this tool fails.
 """
 from __future__ import annotations
@@ -116,13 +121,77 @@ def measure(name: str, dev_frames: torch.Tensor, reps: int) -> dict:
     return case
 
 
+def temporal_frames(kind: str, n: int, size: int, dev) -> torch.Tensor:
+    """``fade`` / ``pan`` of tests/h264_p_ref.py at n x size x size, built in GPU memory from its glyph frames."""
+    import h264_ref as R
+    g = torch.from_numpy(R.make_frames("glyphs", 2, size, size)).to(dev)
+    if kind == "pan":
+        return torch.stack([torch.roll(g[0], k, dims=1) for k in range(n)]).contiguous()
+    a, b = g[0].to(torch.int64), g[1].to(torch.int64)
+    return torch.stack([((a * (2 * (n - 1) - 2 * k) + b * 2 * k + (n - 1)) // (2 * (n - 1))).to(torch.uint8) for k in range(n)]).contiguous()
+
+
+def measure_gop(name: str, dev_frames: torch.Tensor, gop: int, reps: int) -> list:
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    n, H, W, _ = dev_frames.shape
+    mbh, mbw = hip.h264_mb_grid(H, W)
+    y, cb, cr = hip.h264_planes(dev_frames)
+    rows = []
+    for g in (1, gop):
+        enc = H264Encoder(16, dev_frames.device, gop=g)
+        ev, wall = timed(lambda: enc.encode(dev_frames), reps)
+        samples = enc.encode(dev_frames)
+        recon = [torch.empty_like(p) for p in (y, cb, cr)]
+        scratch = torch.empty((hip.h264_gop_scratch_bytes(n, mbh, mbw),), dtype=torch.uint8, device=dev_frames.device)
+        hip.h264_encode_gops(y, cb, cr, 16, g, 0, *recon, scratch)
+        mse = float(((recon[0][:, :H, :W].to(torch.float64) - y[:, :H, :W].to(torch.float64)) ** 2).mean())
+        row = dict(content=name, n=n, H=H, W=W, qp=16, gop=g, chains=-(-n // g) * mbh, encode_ms_events=round(ev, 3), encode_ms_host_clock=round(wall, 3),
+                   frames_per_sec=round(n / wall * 1e3, 1), bytes_per_frame=int(sum(len(s) for s in samples) // n),
+                   y_psnr_db=round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del enc, recon, scratch
+        torch.cuda.empty_cache()
+    return rows
+
+
+def main_gop(args):
+    from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
+    from stable_diffusion_videos_amd.upsampling import RealESRGANModel
+    dev = torch.device("cuda", 0)
+    result = dict(tool=f"tools/h264_bench.py --gop {args.gop}", gpu=torch.cuda.get_device_name(0), host=platform.processor() or platform.machine(),
+                  reps=args.reps, qp=16, rows=[])
+    pipe = StableDiffusionWalkPipeline.from_pretrained("tiny").to(dev)
+    small = pipeline_frames(pipe, 128)
+    up = RealESRGANModel.from_pretrained("nateraw/real-esrgan")
+    up.to(dev)
+    big = torch.cat([up.upsample_u8(small[k:k + 2]) for k in range(0, 8, 2)])
+    del pipe, up
+    for name, make in (("tiny pipeline", lambda: small), ("fade", lambda: temporal_frames("fade", 128, 512, dev)),
+                       ("pan", lambda: temporal_frames("pan", 128, 512, dev)), ("tiny pipeline x4 upsampler", lambda: big),
+                       ("fade", lambda: temporal_frames("fade", 8, 2048, dev)), ("pan", lambda: temporal_frames("pan", 8, 2048, dev))):
+        result["rows"] += measure_gop(name, make().contiguous(), args.gop, args.reps)
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--gop", type=int, default=1, help="N > 1: measure the GOP path, rows for gop 1 and gop N side by side")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("h264_bench needs the GPU (no fallback)")
+    if args.gop != 1:
+        if not 2 <= args.gop <= 256:
+            raise SystemExit("--gop must be 2 .. 256 (1 = the intra measurement)")
+        return main_gop(args)
     from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
     from stable_diffusion_videos_amd.upsampling import RealESRGANModel
     dev = torch.device("cuda", 0)
