@@ -16,7 +16,9 @@
 //   * LDS image is lane-linear (DMA constraint), so the bank-conflict swizzle is applied on the per-lane
 //     SOURCE offset and again on the ds_read_b128 (conflict-free fragment reads for 128-B and 64-B rows).
 //   * v_mfma_f32_32x32x16_bf16 with the WEIGHT rows as the A operand and the ACTIVATION rows as the
-//     B operand: lane l owns output row m = l & 31 and, per accumulator quad, 4 consecutive channels.
+//     B operand: lane l owns output row m = l & 31 and, per accumulator quad, 4 consecutive channels.  The bf16 K loop of the
+//     8-wave tiles runs the same operands through v_mfma_f32_16x16x32_bf16 (row l & 15, channels 4 (l >> 4) .. + 3 per 16 x 16
+//     accumulator): same LDS reads and matrix-pipe cycles, a higher clock under load ("M16" below).
 //   * conv3x3: the K loop walks (tap, source, channel-tile) segments; only segment changes touch VALU.
 //   * Epilogue: fp32 sub-tiles are parked in LDS in 64-column passes and written as whole 128-byte row
 //     segments (16-B coalesced stores, residual loads prefetched before the pass).
@@ -69,7 +71,16 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
     constexpr int TILE_BYTES = (MX ? 2 : 1) * HALF_BYTES;
     constexpr int GX = BM / RPI, GW = BN / RPI;                    // 1-KiB row groups of the X / W panels
     constexpr int NX = (GX + NWV - 1) / NWV, NW = (GW + NWV - 1) / NWV;
-    constexpr int KSTEPS = BK / 16;
+    // M16: the bf16 K loop of the 8-wave tiles runs on v_mfma_f32_16x16x32_bf16 - the same LDS reads, accumulators and matrix-pipe
+    // cycles per K slab as the 32x32x16 form ((TM + TN) x 4 ds_read_b128, TM x TN x 16 fp32 per lane, TM x TN x 128 cycles), but
+    // under these power-limited kernels the chip holds a higher clock on the 16 x 16 shape (profiles/igemm_mfma_shape_ab.txt).
+    // A 32 x 32 tile (nt, mt) is then four 16 x 16 accumulators; lane l owns row 16 hm + (l & 15) and channels
+    // 16 hn + 4 (l >> 4) .. + 3 of it in accumulator (2 nt + hn, 2 mt + hm) - "quad" q = 2 hn + hm of the epilogue.
+    constexpr bool M16 = NWV == 8 && ES == 2;
+    constexpr int MT = M16 ? 16 : 32;                       // edge of an MFMA tile
+    constexpr int AM = TM * 32 / MT, AN = TN * 32 / MT;     // MFMA tiles of a wave along M / N
+    constexpr int RH = M16 ? 2 : 1;                         // 16-row halves of a 32-row m-tile that a lane has quads in
+    constexpr int KSTEPS = BK / (M16 ? 32 : 16);
     static_assert(BM % RPI == 0 && BN % RPI == 0, "panels must be whole 1-KiB groups");
     static_assert(BK == 64 && NST == 2, "64-wide K slabs, double buffered");
     static_assert(FEAT != 2, "(FEAT 2 was the column-side LayerNorm fold of the transposed V^T projections: gone with them)");
@@ -121,9 +132,9 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
     // not keep ~30 addressing registers alive across the epilogue, where the 160 accumulators + the staging state already
     // fill the 256-VGPR budget (they spilled 100-300 B of scratch per lane when simply hoisted out of the tile loop).
     int rg, pc;    // row inside the group one wave-instruction moves / physical 16-B chunk inside the LDS row
-    int l31, lhi;
+    int lrow, lgrp;
     // Fragment reads: every 32-row MFMA tile of either panel starts on a multiple of 32 rows, so the row part of this lane's
-    // read address - l31 * ROWB - and its swizzle term - swz(l31) - are the SAME for all of them: one VGPR per k-step
+    // read address - lrow * ROWB - and its swizzle term - swz(lrow) - are the SAME for all of them: one VGPR per k-step
     // (frag_off[ks]) + a wave-uniform tile base, which ends up in the ds_read's immediate offset.  (An array of per-tile
     // offsets + swizzles cost 2 x (TM + TN) VGPRs and 2-3 VALU per read.)
     int frag_off[KSTEPS];
@@ -329,20 +340,29 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
         }
     };
 
-    f32x16_t acc[TN][TM];
+    std::conditional_t<M16, f32x4_t, f32x16_t> acc[AN][AM];
+    // element e of quad q of the 32 x 32 tile (nt, mt), the row of the m-tile and the first of the 4 consecutive channels of the
+    // n-tile that quad q holds in this lane (32x32x16: row lrow, channels 8 q + 4 lgrp; M16: see above)
+    auto qacc = [&](int nt, int mt, int q, int e) -> float {
+        if constexpr (M16) return acc[2 * nt + (q >> 1)][2 * mt + (q & 1)][e];
+        else return acc[nt][mt][4 * q + e];
+    };
+    auto qrow = [&](int r0, int q) { return M16 ? r0 + 16 * (q & 1) + lrow : r0 + lrow; };
+    auto qcol = [&](int c0, int q) { return M16 ? c0 + 16 * (q >> 1) + 4 * lgrp : c0 + 8 * q + 4 * lgrp; };
 
     auto lane_setup = [&]() {
         int lk = lane;
         if constexpr (PERSIST) asm volatile("" : "+v"(lk));
         rg = lk / CPRW;
         pc = lk % CPRW;
-        l31 = lk & 31;
-        lhi = lk >> 5;
-        static_assert(BM % 32 == 0, "fragment tiles start on multiples of 32 rows (the swizzle term depends on l31 only)");
-        // logical chunk of k-step ks: bf16 tiles 2 ks + lhi (16 bytes = 8 elements); fp8 tiles read chunk 2 j + lhi for the
-        // k-step PAIR j (see compute) - the same expression with ks = j
+        lrow = lk & (MT - 1);
+        lgrp = lk >> (M16 ? 4 : 5);
+        static_assert(BM % 32 == 0, "fragment tiles start on multiples of 16 rows (the swizzle term depends on lrow only)");
+        // logical chunk of k-step ks: bf16 tiles 2 ks + lgrp (16 bytes = 8 elements; M16: 4 ks + lgrp - 32 K values per MFMA, and
+        // the 16 lanes ds_read_b128 serves together still land on 16 different bank groups: 8 swizzle values x 2 row parities);
+        // fp8 tiles read chunk 2 j + lgrp for the k-step PAIR j (see compute) - the same expression with ks = j
 #pragma unroll
-        for (int ks = 0; ks < KSTEPS; ++ks) frag_off[ks] = l31 * ROWB + (((ks * 2 + lhi) ^ swz(l31)) << 4);
+        for (int ks = 0; ks < KSTEPS; ++ks) frag_off[ks] = lrow * ROWB + (((ks * (64 / MT) + lgrp) ^ swz(lrow)) << 4);
     };
 
     // Software-pipelined K tile: the fragments of k-step ks+1 are read into a second register set while the
@@ -351,8 +371,8 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
     auto compute = [&](int buf) {
         const char* base = smem + buf * SLOT;
         if constexpr (MX) {
-            // K image s of the slab feeds ONE 64-deep MFMA per (n, m) tile: lane (l31, lhi) supplies the 16-byte chunks lhi and
-            // 2 + lhi of its row (the two fragment reads of the fp8 tile).  Both operands walk K in that same order, so the
+            // K image s of the slab feeds ONE 64-deep MFMA per (n, m) tile: lane (lrow, lgrp) supplies the 16-byte chunks lgrp and
+            // 2 + lgrp of its row (the two fragment reads of the fp8 tile).  Both operands walk K in that same order, so the
             // contraction is unchanged whatever order the instruction assigns to a lane's 32 bytes.
             typedef int __attribute__((ext_vector_type(8))) i32x8_t;
             constexpr int kOne = 0x7f7f7f7f;   // E8M0 127 = 2^0 in every scale byte
@@ -388,7 +408,7 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
             return;
         }
         if constexpr (ES == 1) {
-            // fp8: a K tile is 64 bytes per row = four 16-byte chunks.  One ds_read_b128 of chunk 2j + lhi yields two
+            // fp8: a K tile is 64 bytes per row = four 16-byte chunks.  One ds_read_b128 of chunk 2j + lgrp yields two
             // 8-byte MFMA operands, used for k-steps 2j and 2j+1 (both operands walk K in the same permuted order, so the
             // contraction is unchanged): 2 fragment reads per row set and K tile feed 4 k-steps.
             typedef __attribute__((ext_vector_type(2))) long long i64x2_t;
@@ -412,20 +432,23 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
                             acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(wq[j][nt][h], xq[j][mt][h], acc[nt][mt], 0, 0, 0);
             return;
         }
+        auto mfma = [](bf16x8_t w, bf16x8_t x, auto c) __attribute__((always_inline)) {
+            if constexpr (M16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
+            else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, x, c, 0, 0, 0);
+        };
         if constexpr (!kPipeFrags) {
             // small wave tiles run 2+ workgroups per CU: other waves cover the LDS latency, registers matter more
 #pragma unroll
             for (int ks = 0; ks < KSTEPS; ++ks) {
-                bf16x8_t xs[TM], ws[TN];
+                bf16x8_t xs[AM], ws[AN];
 #pragma unroll
-                for (int mt = 0; mt < TM; ++mt) xs[mt] = *(const bf16x8_t*)(base + (xrow0 + mt * 32) * ROWB + frag_off[ks]);
+                for (int mt = 0; mt < AM; ++mt) xs[mt] = *(const bf16x8_t*)(base + (xrow0 + mt * MT) * ROWB + frag_off[ks]);
 #pragma unroll
-                for (int nt = 0; nt < TN; ++nt) ws[nt] = *(const bf16x8_t*)(base + (wrow0 + nt * 32) * ROWB + frag_off[ks]);
+                for (int nt = 0; nt < AN; ++nt) ws[nt] = *(const bf16x8_t*)(base + (wrow0 + nt * MT) * ROWB + frag_off[ks]);
 #pragma unroll
-                for (int nt = 0; nt < TN; ++nt)
+                for (int nt = 0; nt < AN; ++nt)
 #pragma unroll
-                    for (int mt = 0; mt < TM; ++mt)
-                        acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ws[nt], xs[mt], acc[nt][mt], 0, 0, 0);
+                    for (int mt = 0; mt < AM; ++mt) acc[nt][mt] = mfma(ws[nt], xs[mt], acc[nt][mt]);
             }
             return;
         }
@@ -437,27 +460,29 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
             // k-steps of a slab and fallen back to read -> s_waitcnt lgkmcnt(0) -> 2 MFMAs per W fragment, the LDS latency of every
             // read exposed (ISA of round 3); here the issue order is pinned by the sched_barriers and every read has AH x TM MFMAs
             // (64 matrix-pipe cycles each pair) to land.  Same accumulation order per output tile: bit-identical results.
-            constexpr int AH = kRotAhead, STEPS = KSTEPS * TN;
-            bf16x8_t xa[2][TM], wq[AH + 1];
+            // M16: the same walk over 16-row fragments - a step is one W fragment against AM = 2 TM X fragments, still 64 matrix-pipe
+            // cycles (4 x 16), so a read still has AH x 64 cycles to land.  The MFMA holds the vector issue for 8 of its 16 cycles:
+            // a step's gaps take the ONE W read of every step, and the AM X reads of the k-step change spread over its 4 gaps.
+            constexpr int AH = kRotAhead, STEPS = KSTEPS * AN;
+            bf16x8_t xa[2][AM], wq[AH + 1];
             auto wfrag = [&](int st) __attribute__((always_inline)) {
-                return *(const bf16x8_t*)(base + (wrow0 + (st % TN) * 32) * ROWB + frag_off[st / TN]);
+                return *(const bf16x8_t*)(base + (wrow0 + (st % AN) * MT) * ROWB + frag_off[st / AN]);
             };
 #pragma unroll
-            for (int mt = 0; mt < TM; ++mt) xa[0][mt] = *(const bf16x8_t*)(base + (xrow0 + mt * 32) * ROWB + frag_off[0]);
+            for (int mt = 0; mt < AM; ++mt) xa[0][mt] = *(const bf16x8_t*)(base + (xrow0 + mt * MT) * ROWB + frag_off[0]);
 #pragma unroll
             for (int a = 0; a < AH; ++a) wq[a] = wfrag(a);
 #pragma unroll
             for (int st = 0; st < STEPS; ++st) {
-                const int ks = st / TN, nt = st % TN;
+                const int ks = st / AN, nt = st % AN;
                 if (st + AH < STEPS) wq[(st + AH) % (AH + 1)] = wfrag(st + AH);
-                if (nt == (TN - 1 - AH >= 0 ? TN - 1 - AH : 0) && ks + 1 < KSTEPS) {
+                if (nt == (AN - 1 - AH >= 0 ? AN - 1 - AH : 0) && ks + 1 < KSTEPS) {
 #pragma unroll
-                    for (int mt = 0; mt < TM; ++mt)
-                        xa[(ks + 1) & 1][mt] = *(const bf16x8_t*)(base + (xrow0 + mt * 32) * ROWB + frag_off[ks + 1]);
+                    for (int mt = 0; mt < AM; ++mt)
+                        xa[(ks + 1) & 1][mt] = *(const bf16x8_t*)(base + (xrow0 + mt * MT) * ROWB + frag_off[ks + 1]);
                 }
 #pragma unroll
-                for (int mt = 0; mt < TM; ++mt)
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[st % (AH + 1)], xa[ks & 1][mt], acc[nt][mt], 0, 0, 0);
+                for (int mt = 0; mt < AM; ++mt) acc[nt][mt] = mfma(wq[st % (AH + 1)], xa[ks & 1][mt], acc[nt][mt]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             return;
@@ -517,10 +542,10 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
             for (int nt = 0; nt < TN; ++nt)
 #pragma unroll
                 for (int mt = 0; mt < TM; ++mt) {
-                    const int m = m0 + wm * TM * 32 + mt * 32 + l31;
+                    const int m = m0 + wm * TM * 32 + mt * 32 + lrow;
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
-                        const int nb = n0 + wn * TN * 32 + nt * 32 + 8 * g4 + 4 * lhi;
+                        const int nb = n0 + wn * TN * 32 + nt * 32 + 8 * g4 + 4 * lgrp;
                         if (m < p.M && nb < p.N)
                             *(float4*)(ws + (long long)m * p.N + nb) = make_float4(acc[nt][mt][4 * g4], acc[nt][mt][4 * g4 + 1],
                                                                                   acc[nt][mt][4 * g4 + 2], acc[nt][mt][4 * g4 + 3]);
@@ -559,7 +584,7 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
         // (the 8-wave tiles compile the three common store sequences only: SiLU - the one extra activation they offer, used
         //  by no network here - takes the register-direct path below; the 4-wave tiles carry the generic sequence as well)
         if (aligned && !p.out_mode && (XACT || p.epi == 0 || (geglu && !R))) {
-            // Staged stores: the MFMA leaves lane (l31, lhi) with row l31 and, per accumulator quad, 4 consecutive columns -
+            // Staged stores: the MFMA leaves lane (lrow, lgrp) with row lrow and, per accumulator quad, 4 consecutive columns -
             // stored as they are, every 16-byte piece of a wave's store instruction lies in a different row, and the texture
             // addresser takes them one by one (measured: 9.5k clocks for the 160 stores of a 256 x 320 tile, the whole K loop
             // of a K = 320 tile is 13k MFMA clocks).  So each wave parks a PASS - 32 rows x 64 bf16 (or 32 fp32 when a
@@ -591,22 +616,25 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
                 __builtin_amdgcn_make_buffer_rsrc((void*)(R ? R + orow0 * p.ldr : C), 0, kRecords, 0x00020000);
             // per-ROW operands of this lane's TM accumulator rows, fetched before the barrier (their latency hides behind it):
             // LayerNorm fold (ln_side 1): (mean, rstd) of the row; bias_mode 2: the row's bias
-            float ln_row[TM][2], bm_[TM];
+            // (M16: a lane's quads sit in the two 16-row halves of an m-tile - one set of row operands per half)
+            float ln_row[TM][RH][2], bm_[TM][RH];
 #pragma unroll
-            for (int mt = 0; mt < TM; ++mt) {
-                ln_row[mt][0] = 0.f;
-                ln_row[mt][1] = 1.f;
-                const int mrow = m0 + wm * TM * 32 + mt * 32 + l31;
-                const bool ok = mrow < p.M;
-                bm_[mt] = (bias && p.bias_mode == 2 && ok) ? bias[mrow] : 0.f;
-                if constexpr (FEAT == 1) {
-                    if (ok) {
-                        const float2 st = *(const float2*)(p.ln_stats + 2 * (bz * p.M + mrow));
-                        ln_row[mt][0] = st.x;
-                        ln_row[mt][1] = st.y;
+            for (int mt = 0; mt < TM; ++mt)
+#pragma unroll
+                for (int h = 0; h < RH; ++h) {
+                    ln_row[mt][h][0] = 0.f;
+                    ln_row[mt][h][1] = 1.f;
+                    const int mrow = qrow(m0 + wm * TM * 32 + mt * 32, h);
+                    const bool ok = mrow < p.M;
+                    bm_[mt][h] = (bias && p.bias_mode == 2 && ok) ? bias[mrow] : 0.f;
+                    if constexpr (FEAT == 1) {
+                        if (ok) {
+                            const float2 st = *(const float2*)(p.ln_stats + 2 * (bz * p.M + mrow));
+                            ln_row[mt][h][0] = st.x;
+                            ln_row[mt][h][1] = st.y;
+                        }
                     }
                 }
-            }
             {
                 // (one element per thread - BN <= 512 - so that the global loads are all issued BEFORE the wait below and
                 //  their latency overlaps the tail of the prefetch instead of following it)
@@ -648,10 +676,13 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
             // the 4 values of accumulator quad q of tile (nt, mt) with scale / LayerNorm fold / bias applied (GEGLU: W rows
             // are interleaved [16 value | 16 gate] per 32-row MFMA tile, so quads g and g+2 of a lane hold the value and the
             // gate of the SAME 4 channels -> quad g in {0, 1} yields 4 of the n-tile's 16 output columns)
+            // (M16: the 16 value rows and the 16 gate rows are the n-tile's two 16 x 16 accumulators hn = 0 / 1 - again quads q and
+            //  q + 2 of the same lane, element for element; q in {0, 1} picks the 16-row half of the m-tile)
             auto quad_vals = [&](bool gg, int nt, int mt, int q, int z, float* v) {   // z: an opaque 0 (see park)
+                const int rh = M16 ? q & 1 : 0;
                 if (gg) {
-                    const float ln_mu = ln_row[mt][0], ar = alpha * ln_row[mt][1];
-                    const int nv = wcol0 + nt * 32 + 8 * q + 4 * lhi - n0 + z;
+                    const float ln_mu = ln_row[mt][rh][0], ar = alpha * ln_row[mt][rh][1];
+                    const int nv = qcol(wcol0 + nt * 32, q) - n0 + z;
                     const float4 bv = *(const float4*)(vbias + nv), bg = *(const float4*)(vbias + nv + 16);
                     float4 sv = make_float4(0.f, 0.f, 0.f, 0.f), sg = sv;
                     if constexpr (ln_side == 1) {
@@ -662,24 +693,24 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
                     const float svv[4] = {sv.x, sv.y, sv.z, sv.w}, sgv[4] = {sg.x, sg.y, sg.z, sg.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        v[e] = ((acc[nt][mt][4 * q + e] - ln_mu * svv[e]) * ar + bvv[e]) *
-                               geglu_gate_f((acc[nt][mt][4 * (q + 2) + e] - ln_mu * sgv[e]) * ar + bgv[e]);
+                        v[e] = ((qacc(nt, mt, q, e) - ln_mu * svv[e]) * ar + bvv[e]) *
+                               geglu_gate_f((qacc(nt, mt, q + 2, e) - ln_mu * sgv[e]) * ar + bgv[e]);
                     return;
                 }
-                const int nb = wcol0 + nt * 32 + 8 * q + 4 * lhi;
+                const int nb = qcol(wcol0 + nt * 32, q);
                 const float al = nb < acols ? alpha : 1.f;    // alpha_cols: scale only the leading output columns
                 const float4 bq = *(const float4*)(vbias + (nb - n0) + z);
-                const float brow = bm_[mt];
+                const float brow = bm_[mt][rh];
                 const float bvv[4] = {bq.x + brow, bq.y + brow, bq.z + brow, bq.w + brow};
                 if constexpr (ln_side == 1) {
                     const float4 s4 = *(const float4*)(vaux + (nb - n0) + z);
                     const float sv4[4] = {s4.x, s4.y, s4.z, s4.w};
-                    const float ar = al * ln_row[mt][1];
+                    const float ar = al * ln_row[mt][rh][1];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (acc[nt][mt][4 * q + e] - ln_row[mt][0] * sv4[e]) * ar + bvv[e];
+                    for (int e = 0; e < 4; ++e) v[e] = (qacc(nt, mt, q, e) - ln_row[mt][rh][0] * sv4[e]) * ar + bvv[e];
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[nt][mt][4 * q + e] * al + bvv[e];
+                    for (int e = 0; e < 4; ++e) v[e] = qacc(nt, mt, q, e) * al + bvv[e];
                 }
             };
 
@@ -758,13 +789,13 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
                             if (gg && q >= 2) continue;
                             float v[4];
                             quad_vals(gg, nt, mt, q, z, v);
-                            const int cl = (gg ? k * 16 : k * 32) + 8 * q + 4 * lhi;   // column inside the pass
+                            const int cl = qcol(gg ? k * 16 : k * 32, q);   // column inside the pass
                             if constexpr (F32) {
-                                *(slab_u4*)(slab + l31 * RS + cl * 4) =
+                                *(slab_u4*)(slab + qrow(0, q) * RS + cl * 4) =
                                     slab_u4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
                             } else {
                                 const slab_u2 pv = slab_u2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-                                *(slab_u2*)(slab + l31 * RS + cl * 2) = pv;
+                                *(slab_u2*)(slab + qrow(0, q) * RS + cl * 2) = pv;
                             }
                         }
                     }
@@ -1032,19 +1063,21 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt)
 #pragma unroll
-            for (int mt = 0; mt < TM; ++mt) {
-                const int m = m0 + wm * TM * 32 + mt * 32 + l31;
+            for (int mh = 0; mh < TM * RH; ++mh) {       // (M16: the 16-row halves of the m-tiles, value quad g = the half)
+                const int mt = mh / RH;
+                const int m = qrow(m0 + wm * TM * 32 + mt * 32, mh % RH);
                 if (m >= p.M) continue;
 #pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    const int nv = wcol0 + nt * 32 + 8 * g + 4 * lhi;  // value row (interleaved index), gate = +16
-                    const int oc = ((wcol0 + nt * 32) >> 1) + 8 * g + 4 * lhi;
+                for (int j = 0; j < 2 / RH; ++j) {
+                    const int g = M16 ? mh % RH : j;
+                    const int nv = qcol(wcol0 + nt * 32, g);  // value row (interleaved index), gate = +16
+                    const int oc = qcol((wcol0 + nt * 32) >> 1, g);
                     if (oc >= nout) continue;
                     float v[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float a = acc[nt][mt][4 * g + e] * alpha;
-                        float gt = acc[nt][mt][4 * (g + 2) + e] * alpha;
+                        float a = qacc(nt, mt, g, e) * alpha;
+                        float gt = qacc(nt, mt, g + 2, e) * alpha;
                         if (bias) {
                             a += bias[nv + e];
                             gt += bias[nv + 16 + e];
@@ -1065,18 +1098,20 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
 #pragma unroll
     for (int nt = 0; nt < TN; ++nt)
 #pragma unroll
-        for (int mt = 0; mt < TM; ++mt) {
-            const int m = m0 + wm * TM * 32 + mt * 32 + l31;
+        for (int mh = 0; mh < TM * RH; ++mh) {           // (M16: the 16-row halves of the m-tiles, quads mh % 2 and mh % 2 + 2)
+            const int mt = mh / RH;
+            const int m = qrow(m0 + wm * TM * 32 + mt * 32, mh % RH);
             if (m >= p.M) continue;
             const float bm_ = (bias && p.bias_mode == 2) ? bias[m] : 0.f;
 #pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int nb = wcol0 + nt * 32 + 8 * g4 + 4 * lhi;
+            for (int j = 0; j < 4 / RH; ++j) {
+                const int g4 = M16 ? mh % RH + 2 * j : j;
+                const int nb = qcol(wcol0 + nt * 32, g4);
                 if (nb >= p.N) continue;
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    v[e] = acc[nt][mt][4 * g4 + e] * (nb < acols ? alpha : 1.f) + bm_;
+                    v[e] = qacc(nt, mt, g4, e) * (nb < acols ? alpha : 1.f) + bm_;
                     if (bias && p.bias_mode == 1 && nb + e < p.N) v[e] += bias[nb + e];
                 }
                 if constexpr (XACT) {
@@ -1168,11 +1203,11 @@ __global__ __launch_bounds__(WM * WN * 64, (((BK == 32 && NST == 2) ? 2 : 1) * W
             }
         }
 #pragma unroll
-        for (int a = 0; a < TN; ++a)
+        for (int a = 0; a < AN; ++a)
 #pragma unroll
-            for (int b = 0; b < TM; ++b)
+            for (int b = 0; b < AM; ++b)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+                for (int e = 0; e < MT * MT / 64; ++e) acc[a][b][e] = 0.f;
         kloop();
         epilogue();
         if (!has_next) break;
