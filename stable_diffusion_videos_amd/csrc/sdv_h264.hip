@@ -5,6 +5,9 @@
 //                          row and frame, each in its own slot of the scratch buffer, plus its length
 //   sdv_h264_encode_gops   planes -> the same slots, but picture k of a call is an IDR picture only when k % gop == 0 and a P picture
 //                          (zero-motion inter prediction from the reconstruction of picture k - 1) otherwise; reconstruction planes
+//   sdv_h264_motion_search, sdv_h264_encode_gop_step (sdv_hip_ext.h "H.264 motion search")
+//                          one even whole-sample vector per macroblock of every P picture from source luma; the GOP path one picture
+//                          position per launch with those vectors
 //   sdv_h264_pack          slots -> one contiguous buffer in sample order, and offsets[n + 1]
 //   sdv_h264_vlc_tables    host only: the VLC tables of the kernel as (length, code) pairs
 //
@@ -20,6 +23,7 @@
 // LDS; lane 0 keeps the DC blocks, the counting pass, the I_PCM decision and the bit writing.
 #include "sdv_common.h"
 #include "sdv_h264_core.h"
+#include "sdv_hip_ext.h"
 
 namespace {
 
@@ -182,6 +186,163 @@ __global__ __launch_bounds__(64) void h264_gops_kernel(const uint8_t* __restrict
     }
 }
 
+// Motion search (sdv_hip_ext.h "H.264 motion search"): one wave per macroblock of every picture of the call, source luma of picture f
+// against source luma of picture f - 1.  The three macroblock columns around the block, 16 + 2 search rows of them, are staged in LDS with
+// 16-byte loads (zeros outside the picture: no admitted candidate reads them); the current block sits in registers.  Lanes own candidates
+// (lane, lane + 64, ...: at most 289), each a plain sum of byte SADs over aligned LDS words shifted into place, so no SAD crosses lanes;
+// the winner is one wave-wide minimum of h264_me_key.  IDR pictures get zeros.
+constexpr int kWinStride = 64;                          // 48 bytes of window, padded: 16-byte stores, and the fifth word of a row's read
+
+__global__ __launch_bounds__(64) void h264_motion_search_kernel(const uint8_t* __restrict__ y, int mbh, int mbw, int qp, int gop, int search,
+                                                                int16_t* __restrict__ mv, int32_t* __restrict__ sad) {
+    __shared__ __attribute__((aligned(16))) uint8_t win[(16 + 2 * kH264SearchMax) * kWinStride];
+    __shared__ __attribute__((aligned(16))) uint8_t cur[256];
+    const int lane = threadIdx.x;
+    const long long id = blockIdx.x;                    // (f * mbh + my) * mbw + mx
+    const int mx = (int)(id % mbw), my = (int)(id / mbw % mbh);
+    const long long f = id / mbw / mbh;
+    if (f % gop == 0) {
+        if (lane == 0) {
+            mv[2 * id] = 0, mv[2 * id + 1] = 0;
+            if (sad) sad[id] = 0;
+        }
+        return;
+    }
+    const long long lw = (long long)mbw * 16;
+    const uint8_t* ref = y + (f - 1) * mbh * 16 * lw;
+    const int rows = 16 + 2 * search, y0 = 16 * my - search;
+    for (int i = lane; i < rows * 3; i += 64) {
+        const int wr = i / 3, j = i % 3, py = y0 + wr, bx = mx - 1 + j;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (py >= 0 && py < 16 * mbh && bx >= 0 && bx < mbw) v = *(const uint4*)(ref + py * lw + bx * 16);
+        *(uint4*)(win + wr * kWinStride + j * 16) = v;
+    }
+    if (lane < 16) *(uint4*)(cur + lane * 16) = *(const uint4*)(y + ((f * mbh + my) * 16 + lane) * lw + mx * 16);
+    __syncthreads();
+    uint32_t c[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) c[i] = ((const uint32_t*)cur)[i];
+    const int per = search + 1, lambda = h264_me_lambda(qp);
+    unsigned best = 0xffffffffu;
+    for (int ci = lane; ci < per * per; ci += 64) {
+        const int vy = 2 * (ci / per) - search, vx = 2 * (ci % per) - search;
+        if (!h264_mv_valid(vx, vy, search, mx, my, mbw, mbh)) continue;
+        const int col = 16 + vx, shift = col & 3;      // 0 or 2: the window's words are aligned, the candidate's samples may not be
+        const uint32_t* q = (const uint32_t*)(win + (search + vy) * kWinStride + (col & ~3));
+        unsigned s = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            uint32_t w[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) w[j] = q[i * (kWinStride / 4) + j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w[j + 1], w[j], (unsigned)shift), c[i * 4 + j], s);
+        }
+        best = min(best, h264_me_key(h264_me_cost((int)s, lambda, vx, vy), vx, vy));
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o));
+    if (lane == 0) {                                    // (0, 0) is always admitted, so there is a winner
+        int cost, vx, vy;
+        h264_me_unkey(best, &cost, &vx, &vy);
+        mv[2 * id] = (int16_t)vx, mv[2 * id + 1] = (int16_t)vy;
+        if (sad) sad[id] = cost - h264_me_cost(0, lambda, vx, vy);
+    }
+}
+
+// h264_gops_kernel's body for ONE picture position k of every GOP, with the vectors of the search: one wave per (GOP, macroblock row).
+// The host enqueues positions 0 .. min(gop, n) - 1 in order: with a vertical component row r of picture f reads rows r - 1 .. r + 1 of
+// the reconstruction of picture f - 1, which other waves wrote, and the kernel boundary orders that.  The reference samples come from
+// the displaced position (2-byte alignment in luma, 1-byte in chroma); a vector of ``mv`` that the stream rule does not admit is coded
+// as (0, 0) (h264_mv_fetch).
+__global__ __launch_bounds__(64) void h264_gop_step_kernel(const uint8_t* __restrict__ y, const uint8_t* __restrict__ cb, const uint8_t* __restrict__ cr,
+                                                           int n, int mbh, int mbw, int qp, int gop, int k, int search, int first_index,
+                                                           const int16_t* __restrict__ mv, uint8_t* ry, uint8_t* rcb, uint8_t* rcr,
+                                                           uint8_t* __restrict__ slots, long long stride, long long slot_bytes,
+                                                           int32_t* __restrict__ lens) {
+    __shared__ h264_gop_mb mb;
+    const int lane = threadIdx.x;
+    const int r = (int)(blockIdx.x % mbh);
+    const long long f = (long long)(blockIdx.x / mbh) * gop + k;
+    if (f >= n) return;
+    const long long lw = (long long)mbw * 16, cw = (long long)mbw * 8;
+    const bool p = k > 0;
+    const long long row = f * mbh + r;
+    uint8_t* slot = slots + row * stride;
+    h264_writer w;
+    h264_chain ch;
+    h264_mv_chain mvc;
+    int skip_run = 0;
+    w.init(slot + 5, slot_bytes - 5);
+    ch.have = 0;
+    mvc.vx = mvc.vy = 0;
+    if (lane == 0) {
+        if (p) h264_p_slice_header(w, (unsigned)(r * mbw), (unsigned)k, qp);
+        else h264_slice_header(w, (unsigned)(r * mbw), (unsigned)((first_index + f) & 1), qp);
+    }
+    const long long yat = row * 16 * lw, cat = row * 8 * cw;                       // this row in picture f
+    const long long ypic = (f - 1) * mbh * 16 * lw, cpic = (f - 1) * mbh * 8 * cw;  // picture f - 1 (read in P pictures only)
+    for (int m = 0; m < mbw; ++m) {
+        h264_mv_ref at;
+        at.vx = at.vy = 0;
+        if (p) {
+            const int16_t* v = mv + (row * mbw + m) * 2;
+            at = h264_mv_fetch(v[0], v[1], search, m, r, mbw, mbh);
+            for (int i = lane; i < 128; i += 64) {      // luma: 16 rows of 8 sample pairs
+                const int a = i >> 3, b = 2 * (i & 7);
+                *(uint16_t*)(mb.fy + a * 16 + b) = *(const uint16_t*)(ry + ypic + at.yoff + a * lw + b);
+            }
+            for (int i = lane; i < 128; i += 64) {      // chroma: 2 x 8 rows of 8 samples
+                const int c = i >> 6, a = (i >> 3) & 7, b = i & 7;
+                mb.fc[c * 64 + a * 8 + b] = (c ? rcr : rcb)[cpic + at.coff + a * cw + b];
+            }
+        }
+        if (lane < 16) {
+            *(uint4*)(mb.sy + lane * 16) = *(const uint4*)(y + yat + lane * lw + m * 16);
+        } else if (lane < 32) {
+            const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+            *(uint2*)(mb.sc + c * 64 + i * 8) = *(const uint2*)((c ? cr : cb) + cat + i * cw + m * 8);
+        }
+        if (lane == 0) h264_gop_pred(&mb, ch);
+        __syncthreads();
+        bool inter = false;
+        if (p) {
+            int si = 0, sp = 0;
+            if (lane < 16) h264_gop_block_sad(&mb, lane, &si, &sp);
+            si = h264_wave_sum(si), sp = h264_wave_sum(sp);
+            inter = !(si < sp);
+        }
+        const bool mine = lane < 24 && h264_gop_block_forward(&mb, lane, inter, qp);
+        const unsigned nz = (unsigned)__ballot(mine);
+        __syncthreads();
+        if (lane == 0) {
+            const bool any_cdc = h264_gop_dc(&mb, inter, qp);
+            h264_gop_serial_mv(&mb, nz, any_cdc, inter, p, ch, mvc, at.vx, at.vy, w, &skip_run);
+        }
+        __syncthreads();
+        if (lane < 24) h264_gop_block_recon(&mb, lane, qp);
+        __syncthreads();
+        if (lane < 16) {
+            *(uint4*)(ry + yat + lane * lw + m * 16) = *(const uint4*)(mb.ry + lane * 16);
+        } else if (lane < 32) {
+            const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+            *(uint2*)((c ? rcr : rcb) + cat + i * cw + m * 8) = *(const uint2*)(mb.rc + c * 64 + i * 8);
+        }
+        if (lane == 0) h264_gop_chain(&mb, ch);
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (p && skip_run) h264_put_ue(w, (unsigned)skip_run);                     // the slice ends in skipped macroblocks
+        w.put(1u, 1);                                   // rbsp_slice_trailing_bits
+        while (w.n) w.put(0u, 1);
+        const long long used = min(w.pos, slot_bytes - 5);      // (the capacity bound keeps pos below it; nothing was stored beyond)
+        const unsigned len = (unsigned)(1 + used);
+        slot[0] = (uint8_t)(len >> 24), slot[1] = (uint8_t)(len >> 16), slot[2] = (uint8_t)(len >> 8), slot[3] = (uint8_t)len;
+        slot[4] = p ? 0x41 : 0x65;                      // nal_ref_idc 2, nal_unit_type 1 | nal_ref_idc 3, nal_unit_type 5
+        lens[row] = (int32_t)(5 + used);
+    }
+}
+
 // ONE workgroup: exclusive scan of the slice lengths, frame-major -> starts[row], offsets[frame], offsets[n]
 __global__ __launch_bounds__(kThreads) void h264_scan_kernel(const int32_t* __restrict__ lens, long long* __restrict__ starts, long long rows, int mbh,
                                                              long long* __restrict__ offsets) {
@@ -300,6 +461,51 @@ extern "C" int sdv_h264_encode_gops(const uint8_t* y, const uint8_t* cb, const u
     hipLaunchKernelGGL(h264_gops_kernel, dim3((unsigned)chains), dim3(64), 0, (hipStream_t)stream, y, cb, cr, n, mbh, mbw, qp, gop, first_index, ry, rcb,
                        rcr, base, l.stride, l.slot, (int32_t*)(base + l.lens_at));
     SDV_CHECK_LAUNCH("sdv_h264_encode_gops");
+    return SDV_OK;
+}
+
+// ---- additive codec extensions of ABI 12 (include/sdv_hip_ext.h) ----
+extern "C" int sdv_h264_motion_search(const uint8_t* y, int32_t n, int32_t mbh, int32_t mbw, int32_t qp, int32_t gop, int32_t search, int16_t* mv,
+                                      int32_t* sad, void* stream) {
+    SDV_REQUIRE(y && mv, "sdv_h264_motion_search: null pointer");
+    H264_GRID_ARGS("sdv_h264_motion_search");
+    SDV_REQUIRE((long long)n * mbh * mbw < 0x7fffffffLL, "sdv_h264_motion_search: too many macroblocks for one grid");
+    SDV_REQUIRE(qp >= 0 && qp <= 51, "sdv_h264_motion_search: qp=%d outside 0 .. 51", qp);
+    SDV_REQUIRE(gop >= 1 && gop <= kH264GopMax, "sdv_h264_motion_search: gop=%d outside 1 .. %d", gop, (int)kH264GopMax);
+    SDV_REQUIRE(search >= 2 && search <= kH264SearchMax && search % 2 == 0, "sdv_h264_motion_search: search=%d must be even, 2 .. %d", search,
+                (int)kH264SearchMax);
+    SDV_REQUIRE((((uintptr_t)y) & 15) == 0 && (((uintptr_t)mv) & 3) == 0 && (((uintptr_t)sad) & 3) == 0,
+                "sdv_h264_motion_search: y must be 16-byte, mv / sad 4-byte aligned");
+    hipLaunchKernelGGL(h264_motion_search_kernel, dim3((unsigned)((long long)n * mbh * mbw)), dim3(64), 0, (hipStream_t)stream, y, mbh, mbw, qp, gop,
+                       search, mv, sad);
+    SDV_CHECK_LAUNCH("sdv_h264_motion_search");
+    return SDV_OK;
+}
+
+extern "C" int sdv_h264_encode_gop_step(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, int32_t n, int32_t mbh, int32_t mbw, int32_t qp,
+                                        int32_t gop, int32_t k, int32_t search, int32_t first_index, const int16_t* mv, uint8_t* ry, uint8_t* rcb,
+                                        uint8_t* rcr, void* scratch, int64_t scratch_bytes, void* stream) {
+    SDV_REQUIRE(y && cb && cr && mv && ry && rcb && rcr && scratch, "sdv_h264_encode_gop_step: null pointer");
+    H264_GRID_ARGS("sdv_h264_encode_gop_step");
+    SDV_REQUIRE(mbw <= 1008, "sdv_h264_encode_gop_step: mbw=%d above 1008 (its slots are those of a wider picture, which must stay within 1024)", mbw);
+    SDV_REQUIRE(qp >= 0 && qp <= 51, "sdv_h264_encode_gop_step: qp=%d outside 0 .. 51", qp);
+    SDV_REQUIRE(gop >= 1 && gop <= kH264GopMax, "sdv_h264_encode_gop_step: gop=%d outside 1 .. %d", gop, (int)kH264GopMax);
+    SDV_REQUIRE(k >= 0 && k < gop && k < n, "sdv_h264_encode_gop_step: position k=%d outside 0 .. min(gop, n) - 1 (gop=%d, n=%d)", k, gop, n);
+    SDV_REQUIRE(search >= 2 && search <= kH264SearchMax && search % 2 == 0, "sdv_h264_encode_gop_step: search=%d must be even, 2 .. %d", search,
+                (int)kH264SearchMax);
+    SDV_REQUIRE(first_index >= 0, "sdv_h264_encode_gop_step: negative first_index");
+    const h264_layout l = h264_scratch_layout(n, mbh, h264_gop_slot_mbw(mbw));
+    SDV_REQUIRE(scratch_bytes >= l.bytes, "sdv_h264_encode_gop_step: scratch buffer too small: %lld bytes, %lld slices of %d macroblocks need %lld",
+                (long long)scratch_bytes, l.rows, mbw, l.bytes);
+    SDV_REQUIRE((((uintptr_t)y) & 15) == 0 && (((uintptr_t)cb) & 7) == 0 && (((uintptr_t)cr) & 7) == 0 && (((uintptr_t)scratch) & 7) == 0,
+                "sdv_h264_encode_gop_step: y must be 16-byte, cb / cr / scratch 8-byte aligned");
+    SDV_REQUIRE((((uintptr_t)ry) & 15) == 0 && (((uintptr_t)rcb) & 7) == 0 && (((uintptr_t)rcr) & 7) == 0 && (((uintptr_t)mv) & 3) == 0,
+                "sdv_h264_encode_gop_step: ry must be 16-byte, rcb / rcr 8-byte, mv 4-byte aligned");
+    uint8_t* base = (uint8_t*)scratch;
+    const long long chains = (long long)((n - k + gop - 1) / gop) * mbh;           // the GOPs that have a picture at position k
+    hipLaunchKernelGGL(h264_gop_step_kernel, dim3((unsigned)chains), dim3(64), 0, (hipStream_t)stream, y, cb, cr, n, mbh, mbw, qp, gop, k, search,
+                       first_index, mv, ry, rcb, rcr, base, l.stride, l.slot, (int32_t*)(base + l.lens_at));
+    SDV_CHECK_LAUNCH("sdv_h264_encode_gop_step");
     return SDV_OK;
 }
 

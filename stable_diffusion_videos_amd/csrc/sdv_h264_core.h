@@ -713,3 +713,157 @@ inline void h264_gop_encode_mb(h264_gop_mb* mb, h264_chain& ch, bool p_slice, in
     for (int b = 0; b < 24; ++b) h264_gop_block_recon(mb, b, qp);
     h264_gop_chain(mb, ch);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Motion-compensated P pictures (sdv_hip_ext.h "H.264 motion search"): one vector per macroblock, every component a multiple of two luma
+// samples, so that luma and chroma predictions are plain displaced copies.  The pieces below are what the search kernel, the per-position
+// GOP kernel and the host share; nothing above this line is touched by them.
+// ------------------------------------------------------------------------------------------------------------------------------------
+enum { kH264SearchMax = 16 };
+
+// lambda(qp) = max(1, round(2 ** ((qp - 12) / 6))): what one bit of a vector costs in units of SAD.  A setting, not a measured optimum.
+H264_HD int h264_me_lambda(int qp) {
+    const uint8_t t[52] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6, 6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20,
+                           23, 25, 29, 32, 36, 40, 45, 51, 57, 64, 72, 81, 91};
+    return t[qp];
+}
+H264_HD int h264_se_bits(int v) {                       // length of se(v)
+    h264_counter c;
+    c.bits = 0, c.failed = false;
+    h264_put_se(c, v);
+    return (int)c.bits;
+}
+// cost(v) = SAD(v) + lambda * (B(vx) + B(vy)), B(c) the length of se(4 c): the vector against a zero predictor
+H264_HD int h264_me_cost(int sad, int lambda, int vx, int vy) { return sad + lambda * (h264_se_bits(4 * vx) + h264_se_bits(4 * vy)); }
+// The total order (cost, |vx| + |vy|, vy, vx) as one unsigned word: cost < 2^17, the three tie fields halved and biased into 5 bits each.
+H264_HD unsigned h264_me_key(int cost, int vx, int vy) {
+    const int a = (vx < 0 ? -vx : vx) + (vy < 0 ? -vy : vy);
+    return ((unsigned)cost << 15) | ((unsigned)(a >> 1) << 10) | ((unsigned)((vy + 16) >> 1) << 5) | (unsigned)((vx + 16) >> 1);
+}
+H264_HD void h264_me_unkey(unsigned key, int* cost, int* vx, int* vy) {
+    *cost = (int)(key >> 15), *vy = 2 * (int)((key >> 5) & 31u) - 16, *vx = 2 * (int)(key & 31u) - 16;
+}
+// A vector the stream rule admits for macroblock (mx, my): even, inside the range, the displaced block wholly inside the padded picture.
+H264_HD bool h264_mv_valid(int vx, int vy, int search, int mx, int my, int mbw, int mbh) {
+    if ((vx & 1) || (vy & 1) || vx < -search || vx > search || vy < -search || vy > search) return false;
+    const int x = 16 * mx + vx, y = 16 * my + vy;
+    return x >= 0 && x + 16 <= 16 * mbw && y >= 0 && y + 16 <= 16 * mbh;
+}
+// Where the prediction of macroblock (mx, my) is fetched from: the vector that is coded (the given one when it is valid, else (0, 0)) and
+// the offsets of the displaced block's first luma / chroma sample from the first sample of the reference picture's planes.
+struct h264_mv_ref {
+    int vx, vy;
+    long long yoff, coff;
+};
+H264_HD h264_mv_ref h264_mv_fetch(int vx, int vy, int search, int mx, int my, int mbw, int mbh) {
+    h264_mv_ref r;
+    const bool ok = h264_mv_valid(vx, vy, search, mx, my, mbw, mbh);
+    r.vx = ok ? vx : 0, r.vy = ok ? vy : 0;
+    r.yoff = (16LL * my + r.vy) * (16LL * mbw) + 16LL * mx + r.vx;
+    r.coff = (8LL * my + r.vy / 2) * (8LL * mbw) + 8LL * mx + r.vx / 2;
+    return r;
+}
+
+// What a macroblock hands to its right neighbour for 8.4.1.3 (B, C and D lie in another slice): its vector when it is inter (P_Skip
+// counts, with (0, 0)), (0, 0) when it is intra or I_PCM or when there is no left neighbour.  Luma samples.
+struct h264_mv_chain {
+    int vx, vy;
+};
+
+// macroblock_layer() of a P_L0_16x16 macroblock with mvd_l0, up to and including the luma residual; cbp 0 carries no mb_qp_delta
+template <class Sink>
+H264_HD void h264_gop_code_inter_mv(const int16_t* lev, int cbp_luma, int cbp_chroma, const h264_chain& left, int mvdx, int mvdy, Sink& s, uint8_t* tcy) {
+    h264_put_ue(s, 0u);                                 // mb_type P_L0_16x16 (ref_idx_l0 is not sent: one active reference)
+    h264_put_se(s, mvdx), h264_put_se(s, mvdy);         // mvd_l0, quarter samples
+    h264_put_ue(s, (unsigned)h264_cbp_inter_code(cbp_luma + 16 * cbp_chroma));
+    if (cbp_luma || cbp_chroma) h264_put_se(s, 0);      // mb_qp_delta
+    for (int b = 0; b < 16; ++b) {
+        if (!((cbp_luma >> (b >> 2)) & 1)) continue;
+        const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+        const int a = bx ? tcy[by * 4 + bx - 1] : left.have ? left.tcy[by] : -1;
+        const int t = by ? tcy[(by - 1) * 4 + bx] : -1;
+        tcy[by * 4 + bx] = (uint8_t)h264_code_block(lev + (1 + b) * 16, 16, h264_nc(a, t), s);
+    }
+}
+template <class Sink>
+H264_HD void h264_gop_code_mb_mv(const int16_t* lev, bool inter, bool p_slice, int cbp_luma, int cbp_chroma, const h264_chain& left, int mvdx, int mvdy,
+                                 Sink& s, uint8_t* tcy, uint8_t* tcc) {
+    for (int i = 0; i < 16; ++i) tcy[i] = 0;            // [by * 4 + bx]
+    for (int i = 0; i < 8; ++i) tcc[i] = 0;             // [c * 4 + by * 2 + bx]
+    if (inter) h264_gop_code_inter_mv(lev, cbp_luma, cbp_chroma, left, mvdx, mvdy, s, tcy);
+    else h264_gop_code_intra(lev, cbp_luma, cbp_chroma, left, p_slice ? 5 : 0, s, tcy, tcc);
+    h264_gop_code_chroma(lev, cbp_chroma, left, s, tcc);
+}
+
+// serial: h264_gop_serial with the macroblock's vector (vx, vy) (luma samples, already through h264_mv_fetch; mb->fy / fc hold the displaced
+// reference).  P_Skip needs cbp 0 and the vector (0, 0); cbp 0 with another vector is P_L0_16x16 with coded_block_pattern codeNum 0.  The
+// counting pass includes the mvd bits.  Leaves in mvc what the right neighbour predicts its vector from.
+H264_HD void h264_gop_serial_mv(h264_gop_mb* mb, unsigned nz, bool any_cdc, bool inter, bool p_slice, h264_chain& ch, h264_mv_chain& mvc, int vx, int vy,
+                                h264_writer& w, int* skip_run) {
+    int cbp_luma = 0;
+    if (inter) {
+        for (int i = 0; i < 4; ++i)
+            if (nz & (0xfu << (4 * i))) cbp_luma |= 1 << i;
+    } else if (nz & 0xffffu) {
+        cbp_luma = 15;
+    }
+    const int cbp_chroma = (nz & 0xff0000u) ? 2 : any_cdc ? 1 : 0;
+    const int mvdx = 4 * (vx - mvc.vx), mvdy = 4 * (vy - mvc.vy);
+    if (inter && !cbp_luma && !cbp_chroma && !vx && !vy) {  // P_Skip: inferred vector (0, 0), no residual
+        ++*skip_run;
+        mb->mode = kH264ModeSkip;
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 0;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 0;
+        mvc.vx = mvc.vy = 0;
+        return;
+    }
+    if (p_slice) {
+        h264_put_ue(w, (unsigned)*skip_run);            // mb_skip_run
+        *skip_run = 0;
+    }
+    uint8_t tcy[16], tcc[8];
+    h264_counter cnt;
+    cnt.bits = 0, cnt.failed = false;
+    h264_gop_code_mb_mv(mb->lev, inter, p_slice, cbp_luma, cbp_chroma, ch, mvdx, mvdy, cnt, tcy, tcc);
+    if (cnt.failed || cnt.bits > 3200) {                // Annex A.3.1 / level_prefix <= 15: I_PCM
+        h264_put_ue(w, p_slice ? 30u : 25u);
+        while (w.n) w.put(0u, 1);                       // pcm_alignment_zero_bit
+        for (int i = 0; i < 256; ++i) w.put(mb->sy[i], 8);
+        for (int i = 0; i < 128; ++i) w.put(mb->sc[i], 8);
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 16;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 16;
+        mb->mode = kH264ModePcm;
+        mvc.vx = mvc.vy = 0;
+        return;
+    }
+    h264_gop_code_mb_mv(mb->lev, inter, p_slice, cbp_luma, cbp_chroma, ch, mvdx, mvdy, w, tcy, tcc);
+    for (int i = 0; i < 4; ++i) ch.tcy[i] = tcy[i * 4 + 3];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 2; ++i) ch.tcc[c][i] = tcc[c * 4 + i * 2 + 1];
+    mb->mode = inter ? kH264ModeInter : kH264ModeIntra;
+    mvc.vx = inter ? vx : 0, mvc.vy = inter ? vy : 0;
+}
+
+// h264_gop_encode_mb with a vector: mb->sy / sc are loaded, and in a P picture mb->fy / fc from the position h264_mv_fetch gave for
+// (vx, vy); leaves mb->ry / rc.  (Host; the kernel spreads the per-block pieces over its lanes.)
+inline void h264_gop_encode_mb_mv(h264_gop_mb* mb, h264_chain& ch, h264_mv_chain& mvc, bool p_slice, int qp, int vx, int vy, h264_writer& w,
+                                  int* skip_run) {
+    h264_gop_pred(mb, ch);
+    bool inter = false;
+    if (p_slice) {
+        int si = 0, sp = 0;
+        for (int b = 0; b < 16; ++b) {
+            int a, c;
+            h264_gop_block_sad(mb, b, &a, &c);
+            si += a, sp += c;
+        }
+        inter = !(si < sp);
+    }
+    unsigned nz = 0;
+    for (int b = 0; b < 24; ++b)
+        if (h264_gop_block_forward(mb, b, inter, qp)) nz |= 1u << b;
+    const bool any_cdc = h264_gop_dc(mb, inter, qp);
+    h264_gop_serial_mv(mb, nz, any_cdc, inter, p_slice, ch, mvc, vx, vy, w, skip_run);
+    for (int b = 0; b < 24; ++b) h264_gop_block_recon(mb, b, qp);
+    h264_gop_chain(mb, ch);
+}

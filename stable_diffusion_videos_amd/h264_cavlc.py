@@ -11,6 +11,10 @@ encoder"); tests/h264_ref.py restates it and decodes it.
 ``k % gop == 0`` and a P picture otherwise: zero-motion inter prediction from the reconstruction of the picture before it, ``P_Skip``
 where nothing is left to code.  tests/h264_p_ref.py restates and decodes that stream.  ``gop`` 1 is the code and the bytes described above.
 
+``search`` > 0 (opt-in on top of ``gop`` > 1; include/sdv_hip_ext.h and DESIGN.md "H.264 motion search") gives every macroblock of a P picture
+one vector of even whole samples, at most ``search`` luma samples a component, found by an exhaustive search on the source pictures: the
+prediction is a displaced copy in luma and chroma.  tests/h264_me_ref.py restates it.  ``search`` 0 is the code and the bytes of ``gop`` alone.
+
 Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
 """
 from __future__ import annotations
@@ -23,6 +27,7 @@ from . import hip
 
 DEFAULT_QP = 16
 DEFAULT_GOP = 1                                                                                 # a setting, not a measured optimum
+DEFAULT_SEARCH = 0                                                                              # a setting, not a measured optimum
 
 
 def check_qp(qp) -> int:
@@ -37,20 +42,29 @@ def check_gop(gop) -> int:
     return gop
 
 
+def check_search(search) -> int:
+    if isinstance(search, bool) or not isinstance(search, int) or not 0 <= search <= hip.H264_SEARCH_MAX or search % 2:
+        raise ValueError(f"h264 search must be an even integer in 0 .. {hip.H264_SEARCH_MAX}, got {search!r}")
+    return search
+
+
 class H264Encoder:
     """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
     (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.  With ``gop``
     > 1 only the pictures at positions ``k % gop == 0`` of a call are IDR pictures (``last_sync`` lists them after every call); the
     others are P pictures, and every call starts a new GOP.  ``return_recon=True`` returns ``(samples, (ry, rcb, rcr))``, the
-    decoder's pictures as padded planes in GPU memory (they belong to the workspace: the next call overwrites them).
+    decoder's pictures as padded planes in GPU memory (they belong to the workspace: the next call overwrites them).  ``search`` > 0
+    (even, at most 16; no effect with ``gop`` 1, which has no P pictures) motion-compensates the P pictures: one more launch for the
+    search over all of them, then one launch per picture position of the GOPs instead of one for all.
 
     Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
     prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
     capacity bound of sdv_hip.h, so no batch can fail to fit."""
 
-    def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP):
+    def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH):
         self.qp = check_qp(qp)
         self.gop = check_gop(gop)
+        self.search = check_search(search)
         self.last_sync: List[int] = []
         self.device = torch.device(device) if device is not None else None
         self._ws: Dict[tuple, dict] = {}
@@ -73,6 +87,8 @@ class H264Encoder:
                       out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True))
             if gops:                                                                            # the reference pictures stay in HBM
                 ws.update(ry=torch.empty_like(ws["y"]), rcb=torch.empty_like(ws["cb"]), rcr=torch.empty_like(ws["cr"]))
+                if self.search:
+                    ws.update(mv=torch.empty((n, mbh, mbw, 2), dtype=torch.int16, device=device))
             if len(self._ws) >= 4:                                                              # a walk uses one or two shapes
                 self._ws.pop(next(iter(self._ws)))
             self._ws[key] = ws
@@ -119,8 +135,14 @@ class H264Encoder:
                 raise hip.SdvHipError("H264Encoder: the all-intra path (gop 1) reconstructs only what its chains read; return_recon needs gop > 1")
             hip.h264_encode_rows(ws["y"], ws["cb"], ws["cr"], self.qp, int(first_index), ws["scratch"])
             hip.h264_pack(ws["scratch"], n, mbh, mbw, ws["out"], ws["offsets"])
-        else:
+        elif self.search == 0:
             hip.h264_encode_gops(ws["y"], ws["cb"], ws["cr"], self.qp, self.gop, int(first_index), ws["ry"], ws["rcb"], ws["rcr"], ws["scratch"])
+            hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
+        else:
+            hip.h264_motion_search(ws["y"], self.qp, self.gop, self.search, ws["mv"])
+            for k in range(min(self.gop, n)):                                                   # the kernel boundary orders picture k - 1 before k
+                hip.h264_encode_gop_step(ws["y"], ws["cb"], ws["cr"], self.qp, self.gop, k, self.search, int(first_index), ws["mv"], ws["ry"],
+                                         ws["rcb"], ws["rcr"], ws["scratch"])
             hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
         self.last_sync = list(range(0, n, self.gop))
         ws["offsets_host"].copy_(ws["offsets"], non_blocking=True)
@@ -138,9 +160,9 @@ class H264Encoder:
 _encoders: Dict[tuple, H264Encoder] = {}
 
 
-def encoder_for(qp: int, device, gop: int = DEFAULT_GOP) -> H264Encoder:
-    """One cached encoder (and its workspaces) per quality setting, GOP length and device."""
-    key = (check_qp(qp), str(device), check_gop(gop))
+def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH) -> H264Encoder:
+    """One cached encoder (and its workspaces) per quality setting, GOP length, search range and device."""
+    key = (check_qp(qp), str(device), check_gop(gop), check_search(search))
     if key not in _encoders:
-        _encoders[key] = H264Encoder(qp, device, gop)
+        _encoders[key] = H264Encoder(qp, device, gop, search)
     return _encoders[key]

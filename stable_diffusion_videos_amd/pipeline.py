@@ -122,6 +122,7 @@ class StableDiffusionWalkPipeline:
         self.video_codec = None            # the dependency-free mp4 writer's codec: None = video.py's default, "h264" / "mjpeg" / "h264-cavlc"; SDV_VIDEO_CODEC wins
         self.h264_qp = 16                  # quantiser of the "h264-cavlc" track (0 .. 51; h264_cavlc.py); SDV_H264_QP wins
         self.h264_gop = 1                  # pictures per IDR picture of the "h264-cavlc" track (1 .. 256; 1 = all intra); SDV_H264_GOP wins
+        self.h264_search = 0               # motion search range of its P pictures in luma samples (even, 0 .. 16; 0 = none); SDV_H264_SEARCH wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
@@ -673,6 +674,21 @@ class StableDiffusionWalkPipeline:
             raise ValueError(f"SDV_H264_GOP / h264_gop must be an integer 1 .. 256, got {gop!r}")
         return gop
 
+    def h264_search_choice(self) -> int:
+        """The motion search range of the P pictures of the ``h264-cavlc`` video track in luma samples: the environment variable
+        SDV_H264_SEARCH (an even integer 0 .. 16) when it is set, else ``self.h264_search``.  0 = zero vectors only; no effect with a GOP
+        length of 1; a setting, not a measured optimum."""
+        env = os.environ.get("SDV_H264_SEARCH")
+        if env is None or env == "":
+            search = self.h264_search
+        elif env.isdigit():
+            search = int(env)
+        else:
+            raise ValueError(f"SDV_H264_SEARCH must be an even integer 0 .. 16, got {env!r}")
+        if isinstance(search, bool) or not isinstance(search, int) or not 0 <= search <= 16 or search % 2:
+            raise ValueError(f"SDV_H264_SEARCH / h264_search must be an even integer 0 .. 16, got {search!r}")
+        return search
+
     def make_clip_frames(self, prompt_a: str, prompt_b: str, seed_a: int, seed_b: int, num_interpolation_steps: int = 5,
                          save_path: Union[str, Path] = "outputs/", num_inference_steps: int = 50,
                          guidance_scale: float = 7.5, eta: float = 0.0, height: Optional[int] = None,
@@ -904,11 +920,13 @@ class StableDiffusionWalkPipeline:
                 make_video_pyav(c["save_path"], audio_filepath=audio_filepath, fps=fps, output_filepath=c["mp4"],
                                 glob_pattern=f"*{image_file_ext}", audio_offset=audio_offset,
                                 audio_duration=num_step / fps, sr=44100, codec=self.video_codec,
-                                h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice())  # :787-796
+                                h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice(),
+                                h264_search=self.h264_search_choice())                       # :787-796
             result = make_video_pyav(save_path_root, audio_filepath=audio_filepath, fps=fps, audio_offset=audio_start_sec,
                                      audio_duration=sum(num_interpolation_steps) / fps, output_filepath=output_filepath,
                                      glob_pattern=f"**/*{image_file_ext}", sr=44100, codec=self.video_codec,
-                                     h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice())   # :798-807
+                                     h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice(),
+                                     h264_search=self.h264_search_choice())                  # :798-807
         if world_size > 1:
             parallel.barrier()
             result = str(output_filepath) if result is None else result

@@ -13,7 +13,9 @@ so that ``walk()`` returns the same ``{name}.mp4`` paths as the reference, in th
 the music video still carries its music; entropy-coded H.264 and AAC need ffmpeg and are what this mode lacks by default.  Opt-in,
 ``SDV_VIDEO_CODEC=h264-cavlc`` (or ``codec="h264-cavlc"``) writes an entropy-coded all-intra H.264 track compressed on the GPU
 (h264_cavlc.py, csrc/sdv_h264.hip) in the same ``avc1`` container; ``h264_gop`` > 1 (the pipeline: ``pipe.h264_gop``,
-``SDV_H264_GOP``) adds P pictures to it (an IDR picture every ``gop`` pictures of an upload batch, an ``stss`` box naming them).
+``SDV_H264_GOP``) adds P pictures to it (an IDR picture every ``gop`` pictures of an upload batch, an ``stss`` box naming them), and
+``h264_search`` > 0 (``pipe.h264_search``, ``SDV_H264_SEARCH``) motion-compensates those with whole-sample vectors; ``LAST_CODEC`` then
+names the range (``"h264 (CAVLC, gop N, search R)"``, ``LAST_CODEC["search"]``).
 Frames are read once each (the reference's pairwise ``torch.cat``
 is O(n^2), :91-93).
 """
@@ -225,11 +227,13 @@ LAST_CODEC: dict = {}
 def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./images", audio_filepath=None, fps: int = 30,
                     audio_offset: int = 0, audio_duration: int = 2, sr: int = 22050,
                     output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png", codec: Optional[str] = None,
-                    h264_qp: Optional[int] = None, h264_gop: Optional[int] = None):
+                    h264_qp: Optional[int] = None, h264_gop: Optional[int] = None, h264_search: Optional[int] = None):
     """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it.  ``codec``: what
     ``SDV_VIDEO_CODEC`` selects (the variable wins): ``"h264"`` (I_PCM), ``"mjpeg"`` or ``"h264-cavlc"`` - the entropy-coded intra
     stream of h264_cavlc.py at quantiser ``h264_qp`` (0 .. 51, default 16), compressed in GPU memory; ``h264_gop``
-    (1 .. 256, default 1) > 1 codes only every ``h264_gop``-th picture as an IDR picture and the others as P pictures."""
+    (1 .. 256, default 1) > 1 codes only every ``h264_gop``-th picture as an IDR picture and the others as P pictures;
+    ``h264_search`` (even, 0 .. 16, default 0) > 0 motion-compensates those P pictures with whole-sample vectors of at most that many
+    luma samples a component (no effect with ``h264_gop`` 1)."""
     output_filepath = str(output_filepath)
     gpu_frames = None                      # a uint8 tensor in GPU memory: a Motion-JPEG track is compressed there (jpeg.py)
     if isinstance(frames_or_frame_dir, torch.Tensor) and frames_or_frame_dir.is_cuda and frames_or_frame_dir.dtype == torch.uint8 \
@@ -269,8 +273,10 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     if codec == "h264-cavlc":
         from .h264_cavlc import DEFAULT_QP, check_qp
         from .h264_cavlc import DEFAULT_GOP, check_gop
+        from .h264_cavlc import DEFAULT_SEARCH, check_search
         qp = check_qp(DEFAULT_QP if h264_qp is None else h264_qp)
         gop = check_gop(DEFAULT_GOP if h264_gop is None else h264_gop)
+        search = check_search(DEFAULT_SEARCH if h264_search is None else h264_search)
         if h % 2 or w % 2:
             codec = "h264"                                                                     # (the odd-size rule below sends it to Motion-JPEG)
         elif gpu_frames is not None:
@@ -304,9 +310,12 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
                       audio="pcm_s16le" if audio is not None else None, why=why)
     if codec == "h264-cavlc" and gop > 1:
         LAST_CODEC["video"] = f"h264 (CAVLC, gop {gop})"
+        if search > 0:
+            LAST_CODEC["video"] = f"h264 (CAVLC, gop {gop}, search {search})"
+            LAST_CODEC["search"] = search
     if codec == "h264-cavlc":
         from .h264_cavlc import encoder_for as h264_encoder_for
-        enc = h264_encoder_for(qp, cavlc_device, gop)
+        enc = h264_encoder_for(qp, cavlc_device, gop, search if gop > 1 else 0)
         step = max(1, H264_BATCH_BYTES // (h * w * 3))                                      # batches of about 64 MB of raw frames
         step = max(gop, step // gop * gop)                                                  # whole GOPs: the file does not depend on it
         sync: Optional[List[int]] = [] if gop > 1 else None

@@ -1,6 +1,6 @@
 """GPU H.264 CAVLC intra encoder (h264_cavlc.H264Encoder) against the two video tracks it can stand in for, on the same box.
 
-    python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N]
+    python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N [--search R[,R...]]]
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -17,6 +17,11 @@ gop 1 - the all-intra code, the comparison - and one for gop N, side by side: en
 frame, and Y-PSNR of the reconstruction of all frames (the planes sdv_h264_encode_gops leaves in HBM; at gop 1 that entry point writes
 the intra stream's bytes).  Frame sets: the tiny pipeline's frames, and the temporal kinds ``fade`` (lerp between two glyph frames) and
 ``pan`` (a glyph frame shifted by k pixels in picture k) of tests/h264_p_ref.py, at 128 x 512 x 512 and 8 x 2048 x 2048.
+With ``--gop N --search R[,R...]`` (each R even, 0 .. 16) the tool measures motion search on top of the GOP path
+(h264_cavlc.H264Encoder(gop=N, search=R)): per frame set one row per R, in the order given - R = 0 is the GOP path without search, the
+comparison of the same run: encode() ms and frames/s, bytes per frame, Y-PSNR of the reconstruction of all frames, and for R > 0 the
+search kernel alone and its share of encode().  Frame sets as with ``--gop`` plus ``pan2``, the glyph frame shifted by 2 k pixels in
+picture k (``pan`` moves one sample a picture, which no even vector matches).
 There is no fallback: without a GPU this tool fails.
 """
 from __future__ import annotations
@@ -125,8 +130,8 @@ def temporal_frames(kind: str, n: int, size: int, dev) -> torch.Tensor:
     """``fade`` / ``pan`` of tests/h264_p_ref.py at n x size x size, built in GPU memory from its glyph frames."""
     import h264_ref as R
     g = torch.from_numpy(R.make_frames("glyphs", 2, size, size)).to(dev)
-    if kind == "pan":
-        return torch.stack([torch.roll(g[0], k, dims=1) for k in range(n)]).contiguous()
+    if kind in ("pan", "pan2"):
+        return torch.stack([torch.roll(g[0], k * (2 if kind == "pan2" else 1), dims=1) for k in range(n)]).contiguous()
     a, b = g[0].to(torch.int64), g[1].to(torch.int64)
     return torch.stack([((a * (2 * (n - 1) - 2 * k) + b * 2 * k + (n - 1)) // (2 * (n - 1))).to(torch.uint8) for k in range(n)]).contiguous()
 
@@ -156,6 +161,32 @@ def measure_gop(name: str, dev_frames: torch.Tensor, gop: int, reps: int) -> lis
     return rows
 
 
+def measure_search(name: str, dev_frames: torch.Tensor, gop: int, searches, reps: int) -> list:
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    n, H, W, _ = dev_frames.shape
+    y = hip.h264_planes(dev_frames)[0]
+    rows = []
+    for search in searches:
+        enc = H264Encoder(16, dev_frames.device, gop=gop, search=search)
+        ev, wall = timed(lambda: enc.encode(dev_frames), reps)
+        samples, recon = enc.encode(dev_frames, return_recon=True)
+        mse = float(((recon[0][:, :H, :W].to(torch.float64) - y[:, :H, :W].to(torch.float64)) ** 2).mean())
+        row = dict(content=name, n=n, H=H, W=W, qp=16, gop=gop, search=search, launches=3 + (1 + min(gop, n) if search else 1),
+                   encode_ms_events=round(ev, 3), encode_ms_host_clock=round(wall, 3), frames_per_sec=round(n / wall * 1e3, 1),
+                   bytes_per_frame=int(sum(len(s) for s in samples) // n), y_psnr_db=round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None)
+        if search:
+            mv = torch.empty((n, y.shape[1] // 16, y.shape[2] // 16, 2), dtype=torch.int16, device=dev_frames.device)
+            ms = timed(lambda: hip.h264_motion_search(y, 16, gop, search, mv), reps)[0]
+            row.update(search_kernel_ms=round(ms, 3), search_share_of_encode=round(ms / ev, 3),
+                       nonzero_vectors=round(float((mv != 0).any(dim=-1).float().mean()), 4))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del enc, recon
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main_gop(args):
     from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
     from stable_diffusion_videos_amd.upsampling import RealESRGANModel
@@ -168,10 +199,18 @@ def main_gop(args):
     up.to(dev)
     big = torch.cat([up.upsample_u8(small[k:k + 2]) for k in range(0, 8, 2)])
     del pipe, up
-    for name, make in (("tiny pipeline", lambda: small), ("fade", lambda: temporal_frames("fade", 128, 512, dev)),
-                       ("pan", lambda: temporal_frames("pan", 128, 512, dev)), ("tiny pipeline x4 upsampler", lambda: big),
-                       ("fade", lambda: temporal_frames("fade", 8, 2048, dev)), ("pan", lambda: temporal_frames("pan", 8, 2048, dev))):
-        result["rows"] += measure_gop(name, make().contiguous(), args.gop, args.reps)
+    sets = [("tiny pipeline", lambda: small), ("fade", lambda: temporal_frames("fade", 128, 512, dev)),
+            ("pan", lambda: temporal_frames("pan", 128, 512, dev)), ("tiny pipeline x4 upsampler", lambda: big),
+            ("fade", lambda: temporal_frames("fade", 8, 2048, dev)), ("pan", lambda: temporal_frames("pan", 8, 2048, dev))]
+    if args.search is not None:
+        result["tool"] += f" --search {args.search}"
+        sets.insert(3, ("pan2", lambda: temporal_frames("pan2", 128, 512, dev)))
+        sets.append(("pan2", lambda: temporal_frames("pan2", 8, 2048, dev)))
+    for name, make in sets:
+        if args.search is not None:
+            result["rows"] += measure_search(name, make().contiguous(), args.gop, args.searches, args.reps)
+        else:
+            result["rows"] += measure_gop(name, make().contiguous(), args.gop, args.reps)
         torch.cuda.empty_cache()
     line = json.dumps(result)
     if args.out:
@@ -185,7 +224,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--gop", type=int, default=1, help="N > 1: measure the GOP path, rows for gop 1 and gop N side by side")
+    ap.add_argument("--search", default=None, help="with --gop N: R[,R...] (even, 0 .. 16): one row per motion search range, 0 = none")
     args = ap.parse_args()
+    if args.search is not None:
+        if args.gop == 1:
+            raise SystemExit("--search needs --gop N > 1 (there are no P pictures at gop 1)")
+        args.searches = [int(v) for v in args.search.split(",")]
+        if any(v % 2 or not 0 <= v <= 16 for v in args.searches):
+            raise SystemExit("--search takes even values 0 .. 16")
     if not torch.cuda.is_available():
         raise SystemExit("h264_bench needs the GPU (no fallback)")
     if args.gop != 1:
