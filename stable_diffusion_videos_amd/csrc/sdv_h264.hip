@@ -8,6 +8,9 @@
 //   sdv_h264_motion_search, sdv_h264_encode_gop_step (sdv_hip_ext.h "H.264 motion search")
 //                          one even whole-sample vector per macroblock of every P picture from source luma; the GOP path one picture
 //                          position per launch with those vectors
+//   sdv_h264_motion_search_sub, sdv_h264_encode_gop_step_sub (sdv_hip_h264_sub.h "H.264 sub-sample motion")
+//                          the same pair with vectors in quarter samples: odd whole, half and quarter samples, 6-tap luma and bilinear
+//                          chroma prediction from clamped LDS windows
 //   sdv_h264_pack          slots -> one contiguous buffer in sample order, and offsets[n + 1]
 //   sdv_h264_vlc_tables    host only: the VLC tables of the kernel as (length, code) pairs
 //
@@ -24,6 +27,7 @@
 #include "sdv_common.h"
 #include "sdv_h264_core.h"
 #include "sdv_hip_ext.h"
+#include "sdv_hip_h264_sub.h"
 
 namespace {
 
@@ -385,6 +389,204 @@ __global__ __launch_bounds__(kThreads) void h264_copy_kernel(const uint8_t* __re
         if (at + i < out_cap) out[at + i] = src[i];
 }
 
+// Sub-sample motion search (sdv_hip_h264_sub.h "H.264 sub-sample motion"): one wave per macroblock again, vectors in quarter samples.
+// The window holds the samples 16 mx - 20 .. 16 mx + 35 of 16 + 2 search + 5 rows that start search + 2 above the block, read with
+// CLAMPED coordinates (an aligned word lies wholly inside or wholly outside the picture: outside it repeats the row's edge sample), so
+// that a fractional candidate at the picture edge finds its filter taps.  Stage 1 is h264_motion_search_kernel's form over every whole
+// sample (shift 0 .. 3, at most 18 candidates a lane).  Stages 2 and 3 take their at most 8 new candidates one after the other: lanes own
+// 4 of the 256 samples, interpolate each straight from the window (h264_sub_luma), and one wave-wide sum gives the SAD to every lane, so
+// the winner is picked uniformly.  The order is h264_sub_key, a 64-bit word.
+constexpr int kSubWinStride = 64;                       // 56 bytes of window, padded
+constexpr int kSubWinLeft = 20;                         // the window's first column lies this far left of the block: >= search + 2, a multiple of 4
+constexpr int kSubWinRows = 16 + 2 * kH264SearchMax + 5;
+
+SDV_DEVICE unsigned long long h264_wave_min64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long other = __shfl_xor(v, o);
+        v = other < v ? other : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void h264_motion_search_sub_kernel(const uint8_t* __restrict__ y, int mbh, int mbw, int qp, int gop, int search,
+                                                                    int subpel, int16_t* __restrict__ mv, int32_t* __restrict__ sad) {
+    __shared__ __attribute__((aligned(16))) uint8_t win[kSubWinRows * kSubWinStride];
+    __shared__ __attribute__((aligned(16))) uint8_t cur[256];
+    const int lane = threadIdx.x;
+    const long long id = blockIdx.x;                    // (f * mbh + my) * mbw + mx
+    const int mx = (int)(id % mbw), my = (int)(id / mbw % mbh);
+    const long long f = id / mbw / mbh;
+    if (f % gop == 0) {
+        if (lane == 0) {
+            mv[2 * id] = 0, mv[2 * id + 1] = 0;
+            if (sad) sad[id] = 0;
+        }
+        return;
+    }
+    const long long lw = (long long)mbw * 16;
+    const uint8_t* ref = y + (f - 1) * mbh * 16 * lw;
+    const int rows = 16 + 2 * search + 5, y0 = 16 * my - search - 2, x0 = 16 * mx - kSubWinLeft;
+    for (int i = lane; i < rows * 14; i += 64) {
+        const int wr = i / 14, j = i % 14, px = x0 + 4 * j;
+        const uint8_t* line = ref + (long long)h264_sub_clampi(y0 + wr, 16 * mbh - 1) * lw;
+        const uint32_t v = px < 0 ? line[0] * 0x01010101u : px >= 16 * mbw ? line[16 * mbw - 1] * 0x01010101u : *(const uint32_t*)(line + px);
+        *(uint32_t*)(win + wr * kSubWinStride + 4 * j) = v;
+    }
+    if (lane < 16) *(uint4*)(cur + lane * 16) = *(const uint4*)(y + ((f * mbh + my) * 16 + lane) * lw + mx * 16);
+    __syncthreads();
+    const int lambda = h264_me_lambda(qp);
+    unsigned long long best = ~0ull;
+    {
+        uint32_t c[64];
+#pragma unroll
+        for (int i = 0; i < 64; ++i) c[i] = ((const uint32_t*)cur)[i];
+        const int per = 2 * search + 1;
+        for (int ci = lane; ci < per * per; ci += 64) {
+            const int vy = ci / per - search, vx = ci % per - search;              // whole samples
+            if (!h264_sub_valid(4 * vx, 4 * vy, search, 1, mx, my, mbw, mbh)) continue;
+            const int col = kSubWinLeft + vx, shift = col & 3;
+            const uint32_t* q = (const uint32_t*)(win + (search + 2 + vy) * kSubWinStride + (col & ~3));
+            unsigned s = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                uint32_t w[5];
+#pragma unroll
+                for (int j = 0; j < 5; ++j) w[j] = q[i * (kSubWinStride / 4) + j];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w[j + 1], w[j], (unsigned)shift), c[i * 4 + j], s);
+            }
+            const unsigned long long key = h264_sub_key(h264_sub_cost((int)s, lambda, 4 * vx, 4 * vy), 4 * vx, 4 * vy);
+            best = key < best ? key : best;
+        }
+    }
+    best = h264_wave_min64(best);                       // (0, 0) is always admitted, so there is a winner
+    const int r = lane >> 2, c0 = 4 * (lane & 3);       // stages 2 and 3: this lane's four samples
+    for (int step = 2; step * subpel >= 4; step >>= 1) {
+        int cost, cx, cy;
+        h264_sub_unkey(best, &cost, &cx, &cy);
+        for (int d = 0; d < 9; ++d) {
+            const int vx = cx + step * (d % 3 - 1), vy = cy + step * (d / 3 - 1);
+            if (d == 4 || !h264_sub_valid(vx, vy, search, subpel, mx, my, mbw, mbh)) continue;
+            const uint8_t* g = win + (search + 2 + (vy >> 2) + r) * kSubWinStride + kSubWinLeft + (vx >> 2) + c0;
+            int s = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int diff = (int)cur[r * 16 + c0 + e] - h264_sub_luma(g + e, kSubWinStride, vx & 3, vy & 3);
+                s += diff < 0 ? -diff : diff;
+            }
+            s = h264_wave_sum(s);
+            const unsigned long long key = h264_sub_key(h264_sub_cost(s, lambda, vx, vy), vx, vy);
+            best = key < best ? key : best;
+        }
+    }
+    if (lane == 0) {
+        int cost, vx, vy;
+        h264_sub_unkey(best, &cost, &vx, &vy);
+        mv[2 * id] = (int16_t)vx, mv[2 * id + 1] = (int16_t)vy;
+        if (sad) sad[id] = cost - h264_sub_cost(0, lambda, vx, vy);
+    }
+}
+
+// h264_gop_step_kernel with quarter-sample vectors: for a P macroblock the 21 x 21 luma window and the two 9 x 9 chroma windows of the
+// reference RECONSTRUCTION are staged in LDS with clamped coordinates (no read leaves a plane, whatever the vector), then every lane
+// interpolates 4 luma and 2 chroma samples of mb.fy / mb.fc.  Whole-sample vectors take the same path: fraction 0 is a copy.  A vector of
+// ``mv`` that is off the subpel grid, out of range or not admitted is coded as (0, 0) (h264_sub_fetch).  Everything after the prediction
+// is h264_gop_step_kernel's code with the vector and the chain in quarter samples.
+__global__ __launch_bounds__(64) void h264_gop_step_sub_kernel(const uint8_t* __restrict__ y, const uint8_t* __restrict__ cb,
+                                                               const uint8_t* __restrict__ cr, int n, int mbh, int mbw, int qp, int gop, int k,
+                                                               int search, int subpel, int first_index, const int16_t* __restrict__ mv, uint8_t* ry,
+                                                               uint8_t* rcb, uint8_t* rcr, uint8_t* __restrict__ slots, long long stride,
+                                                               long long slot_bytes, int32_t* __restrict__ lens) {
+    constexpr int kLuma = kH264SubLumaWin * kH264SubLumaWin, kChroma = kH264SubChromaWin * kH264SubChromaWin;
+    __shared__ h264_gop_mb mb;
+    __shared__ uint8_t wy[kLuma];
+    __shared__ uint8_t wc[2 * kChroma];
+    const int lane = threadIdx.x;
+    const int r = (int)(blockIdx.x % mbh);
+    const long long f = (long long)(blockIdx.x / mbh) * gop + k;
+    if (f >= n) return;
+    const long long lw = (long long)mbw * 16, cw = (long long)mbw * 8;
+    const bool p = k > 0;
+    const long long row = f * mbh + r;
+    uint8_t* slot = slots + row * stride;
+    h264_writer w;
+    h264_chain ch;
+    h264_mv_chain mvc;
+    int skip_run = 0;
+    w.init(slot + 5, slot_bytes - 5);
+    ch.have = 0;
+    mvc.vx = mvc.vy = 0;
+    if (lane == 0) {
+        if (p) h264_p_slice_header(w, (unsigned)(r * mbw), (unsigned)k, qp);
+        else h264_slice_header(w, (unsigned)(r * mbw), (unsigned)((first_index + f) & 1), qp);
+    }
+    const long long yat = row * 16 * lw, cat = row * 8 * cw;                       // this row in picture f
+    const long long ypic = (f - 1) * mbh * 16 * lw, cpic = (f - 1) * mbh * 8 * cw;  // picture f - 1 (read in P pictures only)
+    for (int m = 0; m < mbw; ++m) {
+        h264_sub_ref at = h264_sub_fetch(0, 0, search, subpel, m, r, mbw, mbh);
+        if (p) {
+            const int16_t* v = mv + (row * mbw + m) * 2;
+            at = h264_sub_fetch(v[0], v[1], search, subpel, m, r, mbw, mbh);
+            for (int i = lane; i < kLuma; i += 64) wy[i] = ry[ypic + h264_sub_luma_at(at, i, m, r, mbw, mbh)];
+            for (int i = lane; i < 2 * kChroma; i += 64)
+                wc[i] = (i < kChroma ? rcb : rcr)[cpic + h264_sub_chroma_at(at, i % kChroma, m, r, mbw, mbh)];
+            __syncthreads();
+            {
+                const int a = lane >> 2, b = 4 * (lane & 3);                       // luma: 4 samples of row a
+#pragma unroll
+                for (int e = 0; e < 4; ++e) mb.fy[a * 16 + b + e] = (uint8_t)h264_sub_pred_luma(wy, at, b + e, a);
+                const int c = lane >> 5, ca = (lane >> 2) & 7, cb2 = 2 * (lane & 3);   // chroma: 2 samples of row ca of component c
+#pragma unroll
+                for (int e = 0; e < 2; ++e) mb.fc[c * 64 + ca * 8 + cb2 + e] = (uint8_t)h264_sub_pred_chroma(wc + c * kChroma, at, cb2 + e, ca);
+            }
+        }
+        if (lane < 16) {
+            *(uint4*)(mb.sy + lane * 16) = *(const uint4*)(y + yat + lane * lw + m * 16);
+        } else if (lane < 32) {
+            const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+            *(uint2*)(mb.sc + c * 64 + i * 8) = *(const uint2*)((c ? cr : cb) + cat + i * cw + m * 8);
+        }
+        if (lane == 0) h264_gop_pred(&mb, ch);
+        __syncthreads();
+        bool inter = false;
+        if (p) {
+            int si = 0, sp = 0;
+            if (lane < 16) h264_gop_block_sad(&mb, lane, &si, &sp);
+            si = h264_wave_sum(si), sp = h264_wave_sum(sp);
+            inter = !(si < sp);
+        }
+        const bool mine = lane < 24 && h264_gop_block_forward(&mb, lane, inter, qp);
+        const unsigned nz = (unsigned)__ballot(mine);
+        __syncthreads();
+        if (lane == 0) {
+            const bool any_cdc = h264_gop_dc(&mb, inter, qp);
+            h264_gop_serial_sub(&mb, nz, any_cdc, inter, p, ch, mvc, at.vx, at.vy, w, &skip_run);
+        }
+        __syncthreads();
+        if (lane < 24) h264_gop_block_recon(&mb, lane, qp);
+        __syncthreads();
+        if (lane < 16) {
+            *(uint4*)(ry + yat + lane * lw + m * 16) = *(const uint4*)(mb.ry + lane * 16);
+        } else if (lane < 32) {
+            const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+            *(uint2*)((c ? rcr : rcb) + cat + i * cw + m * 8) = *(const uint2*)(mb.rc + c * 64 + i * 8);
+        }
+        if (lane == 0) h264_gop_chain(&mb, ch);
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (p && skip_run) h264_put_ue(w, (unsigned)skip_run);                     // the slice ends in skipped macroblocks
+        w.put(1u, 1);                                   // rbsp_slice_trailing_bits
+        while (w.n) w.put(0u, 1);
+        const long long used = min(w.pos, slot_bytes - 5);      // (the capacity bound keeps pos below it; nothing was stored beyond)
+        const unsigned len = (unsigned)(1 + used);
+        slot[0] = (uint8_t)(len >> 24), slot[1] = (uint8_t)(len >> 16), slot[2] = (uint8_t)(len >> 8), slot[3] = (uint8_t)len;
+        slot[4] = p ? 0x41 : 0x65;                      // nal_ref_idc 2, nal_unit_type 1 | nal_ref_idc 3, nal_unit_type 5
+        lens[row] = (int32_t)(5 + used);
+    }
+}
+
 struct h264_layout {
     long long rows, slot, stride, starts_at, lens_at, bytes;
 };
@@ -506,6 +708,54 @@ extern "C" int sdv_h264_encode_gop_step(const uint8_t* y, const uint8_t* cb, con
     hipLaunchKernelGGL(h264_gop_step_kernel, dim3((unsigned)chains), dim3(64), 0, (hipStream_t)stream, y, cb, cr, n, mbh, mbw, qp, gop, k, search,
                        first_index, mv, ry, rcb, rcr, base, l.stride, l.slot, (int32_t*)(base + l.lens_at));
     SDV_CHECK_LAUNCH("sdv_h264_encode_gop_step");
+    return SDV_OK;
+}
+
+// ---- sub-sample motion (include/sdv_hip_h264_sub.h): the two entry points above with vectors in quarter samples ----
+extern "C" int sdv_h264_motion_search_sub(const uint8_t* y, int32_t n, int32_t mbh, int32_t mbw, int32_t qp, int32_t gop, int32_t search,
+                                          int32_t subpel, int16_t* mv, int32_t* sad, void* stream) {
+    SDV_REQUIRE(y && mv, "sdv_h264_motion_search_sub: null pointer");
+    H264_GRID_ARGS("sdv_h264_motion_search_sub");
+    SDV_REQUIRE((long long)n * mbh * mbw < 0x7fffffffLL, "sdv_h264_motion_search_sub: too many macroblocks for one grid");
+    SDV_REQUIRE(qp >= 0 && qp <= 51, "sdv_h264_motion_search_sub: qp=%d outside 0 .. 51", qp);
+    SDV_REQUIRE(gop >= 1 && gop <= kH264GopMax, "sdv_h264_motion_search_sub: gop=%d outside 1 .. %d", gop, (int)kH264GopMax);
+    SDV_REQUIRE(search >= 2 && search <= kH264SearchMax && search % 2 == 0, "sdv_h264_motion_search_sub: search=%d must be even, 2 .. %d", search,
+                (int)kH264SearchMax);
+    SDV_REQUIRE(h264_subpel_ok(subpel), "sdv_h264_motion_search_sub: subpel=%d must be 1, 2 or 4", subpel);
+    SDV_REQUIRE((((uintptr_t)y) & 15) == 0 && (((uintptr_t)mv) & 3) == 0 && (((uintptr_t)sad) & 3) == 0,
+                "sdv_h264_motion_search_sub: y must be 16-byte, mv / sad 4-byte aligned");
+    hipLaunchKernelGGL(h264_motion_search_sub_kernel, dim3((unsigned)((long long)n * mbh * mbw)), dim3(64), 0, (hipStream_t)stream, y, mbh, mbw, qp,
+                       gop, search, subpel, mv, sad);
+    SDV_CHECK_LAUNCH("sdv_h264_motion_search_sub");
+    return SDV_OK;
+}
+
+extern "C" int sdv_h264_encode_gop_step_sub(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, int32_t n, int32_t mbh, int32_t mbw, int32_t qp,
+                                            int32_t gop, int32_t k, int32_t search, int32_t subpel, int32_t first_index, const int16_t* mv,
+                                            uint8_t* ry, uint8_t* rcb, uint8_t* rcr, void* scratch, int64_t scratch_bytes, void* stream) {
+    SDV_REQUIRE(y && cb && cr && mv && ry && rcb && rcr && scratch, "sdv_h264_encode_gop_step_sub: null pointer");
+    H264_GRID_ARGS("sdv_h264_encode_gop_step_sub");
+    SDV_REQUIRE(mbw <= 1008, "sdv_h264_encode_gop_step_sub: mbw=%d above 1008 (its slots are those of a wider picture, which must stay within 1024)",
+                mbw);
+    SDV_REQUIRE(qp >= 0 && qp <= 51, "sdv_h264_encode_gop_step_sub: qp=%d outside 0 .. 51", qp);
+    SDV_REQUIRE(gop >= 1 && gop <= kH264GopMax, "sdv_h264_encode_gop_step_sub: gop=%d outside 1 .. %d", gop, (int)kH264GopMax);
+    SDV_REQUIRE(k >= 0 && k < gop && k < n, "sdv_h264_encode_gop_step_sub: position k=%d outside 0 .. min(gop, n) - 1 (gop=%d, n=%d)", k, gop, n);
+    SDV_REQUIRE(search >= 2 && search <= kH264SearchMax && search % 2 == 0, "sdv_h264_encode_gop_step_sub: search=%d must be even, 2 .. %d", search,
+                (int)kH264SearchMax);
+    SDV_REQUIRE(h264_subpel_ok(subpel), "sdv_h264_encode_gop_step_sub: subpel=%d must be 1, 2 or 4", subpel);
+    SDV_REQUIRE(first_index >= 0, "sdv_h264_encode_gop_step_sub: negative first_index");
+    const h264_layout l = h264_scratch_layout(n, mbh, h264_gop_slot_mbw(mbw));
+    SDV_REQUIRE(scratch_bytes >= l.bytes, "sdv_h264_encode_gop_step_sub: scratch buffer too small: %lld bytes, %lld slices of %d macroblocks need %lld",
+                (long long)scratch_bytes, l.rows, mbw, l.bytes);
+    SDV_REQUIRE((((uintptr_t)y) & 15) == 0 && (((uintptr_t)cb) & 7) == 0 && (((uintptr_t)cr) & 7) == 0 && (((uintptr_t)scratch) & 7) == 0,
+                "sdv_h264_encode_gop_step_sub: y must be 16-byte, cb / cr / scratch 8-byte aligned");
+    SDV_REQUIRE((((uintptr_t)ry) & 15) == 0 && (((uintptr_t)rcb) & 7) == 0 && (((uintptr_t)rcr) & 7) == 0 && (((uintptr_t)mv) & 3) == 0,
+                "sdv_h264_encode_gop_step_sub: ry must be 16-byte, rcb / rcr 8-byte, mv 4-byte aligned");
+    uint8_t* base = (uint8_t*)scratch;
+    const long long chains = (long long)((n - k + gop - 1) / gop) * mbh;           // the GOPs that have a picture at position k
+    hipLaunchKernelGGL(h264_gop_step_sub_kernel, dim3((unsigned)chains), dim3(64), 0, (hipStream_t)stream, y, cb, cr, n, mbh, mbw, qp, gop, k, search,
+                       subpel, first_index, mv, ry, rcb, rcr, base, l.stride, l.slot, (int32_t*)(base + l.lens_at));
+    SDV_CHECK_LAUNCH("sdv_h264_encode_gop_step_sub");
     return SDV_OK;
 }
 

@@ -867,3 +867,174 @@ inline void h264_gop_encode_mb_mv(h264_gop_mb* mb, h264_chain& ch, h264_mv_chain
     for (int b = 0; b < 24; ++b) h264_gop_block_recon(mb, b, qp);
     h264_gop_chain(mb, ch);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Sub-sample motion (sdv_hip_h264_sub.h "H.264 sub-sample motion"): vectors in QUARTER luma samples on a grid of 4 / subpel quarters,
+// 6-tap luma (8.4.2.2.1) and bilinear chroma (8.4.2.2.2) prediction.  The two functions below are the only interpolators: the search's
+// refinement, the per-position GOP kernel and the host build all read a staged window through them.  Nothing above is touched.
+// ------------------------------------------------------------------------------------------------------------------------------------
+H264_HD int h264_sub_tap6(const uint8_t* p, int step) {                           // E - 5F + 20G + 20H - 5I + J, p at G
+    return (int)p[-2 * step] - 5 * (int)p[-step] + 20 * (int)p[0] + 20 * (int)p[step] - 5 * (int)p[2 * step] + (int)p[3 * step];
+}
+H264_HD int h264_sub_half(int v1) { return h264_clip255((v1 + 16) >> 5); }
+// One luma sample: ``g`` points at the whole sample G of the integer part inside a staged window of row length ``stride`` that holds
+// two more samples before and three after G in both directions; (xf, yf) in 0 .. 3 are the quarter fractions.
+H264_HD int h264_sub_luma(const uint8_t* g, int stride, int xf, int yf) {
+    if (!(xf | yf)) return g[0];
+    if (!yf) {                                          // a, b, c
+        const int b = h264_sub_half(h264_sub_tap6(g, 1));
+        return xf == 2 ? b : ((int)g[xf >> 1] + b + 1) >> 1;
+    }
+    if (!xf) {                                          // d, h, n
+        const int h = h264_sub_half(h264_sub_tap6(g, stride));
+        return yf == 2 ? h : ((int)g[(yf >> 1) * stride] + h + 1) >> 1;
+    }
+    if ((xf & 1) && (yf & 1)) {                         // e, g, p, r: the b-type sample of row yf >> 1 and the h-type sample of column xf >> 1
+        const int b = h264_sub_half(h264_sub_tap6(g + (yf >> 1) * stride, 1));
+        const int h = h264_sub_half(h264_sub_tap6(g + (xf >> 1), stride));
+        return (b + h + 1) >> 1;
+    }
+    const int j1 = h264_sub_tap6(g - 2 * stride, 1) - 5 * h264_sub_tap6(g - stride, 1) + 20 * h264_sub_tap6(g, 1) +
+                   20 * h264_sub_tap6(g + stride, 1) - 5 * h264_sub_tap6(g + 2 * stride, 1) + h264_sub_tap6(g + 3 * stride, 1);
+    const int j = h264_clip255((j1 + 512) >> 10);       // j: the 6-tap over the unclipped row intermediates
+    if (xf == 2 && yf == 2) return j;
+    if (xf == 2) return (h264_sub_half(h264_sub_tap6(g + (yf >> 1) * stride, 1)) + j + 1) >> 1;      // f, q: b or s
+    return (h264_sub_half(h264_sub_tap6(g + (xf >> 1), stride)) + j + 1) >> 1;                        // i, k: h or m
+}
+// One chroma sample: ``a`` points at sample A of the integer part (B right of it, C below, D diagonal); (xf, yf) in 0 .. 7.
+H264_HD int h264_sub_chroma(const uint8_t* a, int stride, int xf, int yf) {
+    return ((8 - xf) * (8 - yf) * (int)a[0] + xf * (8 - yf) * (int)a[1] + (8 - xf) * yf * (int)a[stride] + xf * yf * (int)a[stride + 1] + 32) >> 6;
+}
+enum { kH264SubLumaWin = 21, kH264SubChromaWin = 9 };   // a macroblock's windows: 16 + 5 luma rows / columns, 8 + 1 chroma
+
+H264_HD bool h264_subpel_ok(int subpel) { return subpel == 1 || subpel == 2 || subpel == 4; }
+// A vector (quarter samples) the rule admits for macroblock (mx, my): on the grid, inside the range, the whole samples around the displaced
+// block (floor and ceiling of the position) inside the padded picture.  The filter taps beyond them are read clamped.
+H264_HD bool h264_sub_valid(int vx, int vy, int search, int subpel, int mx, int my, int mbw, int mbh) {
+    const int off = 4 / subpel - 1;
+    if ((vx & off) || (vy & off) || vx < -4 * search || vx > 4 * search || vy < -4 * search || vy > 4 * search) return false;
+    const int x0 = 16 * mx + (vx >> 2), x1 = 16 * mx + ((vx + 3) >> 2), y0 = 16 * my + (vy >> 2), y1 = 16 * my + ((vy + 3) >> 2);
+    return x0 >= 0 && x1 + 16 <= 16 * mbw && y0 >= 0 && y1 + 16 <= 16 * mbh;
+}
+// The vector that is coded (the given one when it is valid, else (0, 0)), split into whole-sample offsets and fractions for both planes.
+struct h264_sub_ref {
+    int vx, vy;                                         // quarter luma samples = eighth chroma samples
+    int ix, iy, xf, yf;                                 // luma: floor(v / 4), v & 3
+    int cix, ciy, cxf, cyf;                             // chroma: floor(v / 8), v & 7
+};
+H264_HD h264_sub_ref h264_sub_fetch(int vx, int vy, int search, int subpel, int mx, int my, int mbw, int mbh) {
+    h264_sub_ref r;
+    const bool ok = h264_sub_valid(vx, vy, search, subpel, mx, my, mbw, mbh);
+    r.vx = ok ? vx : 0, r.vy = ok ? vy : 0;
+    r.ix = r.vx >> 2, r.iy = r.vy >> 2, r.xf = r.vx & 3, r.yf = r.vy & 3;
+    r.cix = r.vx >> 3, r.ciy = r.vy >> 3, r.cxf = r.vx & 7, r.cyf = r.vy & 7;
+    return r;
+}
+H264_HD int h264_sub_clampi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
+// Sample i of a macroblock's clamped window: luma window sample (row i / 21, column i % 21) of the 21 x 21 samples that start two before
+// the displaced block's integer position, chroma (i / 9, i % 9) of the 9 x 9 that start at it.  Offsets into the reference picture's plane.
+H264_HD long long h264_sub_luma_at(const h264_sub_ref& at, int i, int mx, int my, int mbw, int mbh) {
+    const int py = h264_sub_clampi(16 * my + at.iy - 2 + i / kH264SubLumaWin, 16 * mbh - 1);
+    const int px = h264_sub_clampi(16 * mx + at.ix - 2 + i % kH264SubLumaWin, 16 * mbw - 1);
+    return (long long)py * (16LL * mbw) + px;
+}
+H264_HD long long h264_sub_chroma_at(const h264_sub_ref& at, int i, int mx, int my, int mbw, int mbh) {
+    const int py = h264_sub_clampi(8 * my + at.ciy + i / kH264SubChromaWin, 8 * mbh - 1);
+    const int px = h264_sub_clampi(8 * mx + at.cix + i % kH264SubChromaWin, 8 * mbw - 1);
+    return (long long)py * (8LL * mbw) + px;
+}
+// Prediction sample (x, y) of the macroblock from its staged windows (wy: 21 x 21, wc: 9 x 9 of one component)
+H264_HD int h264_sub_pred_luma(const uint8_t* wy, const h264_sub_ref& at, int x, int y) {
+    return h264_sub_luma(wy + (y + 2) * kH264SubLumaWin + x + 2, kH264SubLumaWin, at.xf, at.yf);
+}
+H264_HD int h264_sub_pred_chroma(const uint8_t* wc, const h264_sub_ref& at, int x, int y) {
+    return h264_sub_chroma(wc + y * kH264SubChromaWin + x, kH264SubChromaWin, at.cxf, at.cyf);
+}
+
+// cost(v) = SAD(v) + lambda * (B(vx) + B(vy)), B(c) the length of se(c), c in quarter samples (for whole samples h264_me_cost's se(4 c))
+H264_HD int h264_sub_cost(int sad, int lambda, int vx, int vy) { return sad + lambda * (h264_se_bits(vx) + h264_se_bits(vy)); }
+// The total order (cost, |vx| + |vy|, vy, vx) in quarter samples as one 64-bit word: |v| <= 64, so 8 bits hold a biased component.
+H264_HD unsigned long long h264_sub_key(int cost, int vx, int vy) {
+    const int a = (vx < 0 ? -vx : vx) + (vy < 0 ? -vy : vy);
+    return ((unsigned long long)(unsigned)cost << 32) | ((unsigned long long)a << 16) | ((unsigned long long)(vy + 64) << 8) | (unsigned long long)(vx + 64);
+}
+H264_HD void h264_sub_unkey(unsigned long long key, int* cost, int* vx, int* vy) {
+    *cost = (int)(key >> 32), *vy = (int)((key >> 8) & 255u) - 64, *vx = (int)(key & 255u) - 64;
+}
+
+// serial: h264_gop_serial_mv with the vector (vx, vy) and the chain ``mvc`` in QUARTER samples (already through h264_sub_fetch; mb->fy /
+// fc hold the interpolated prediction), so mvd = v - mvp without a scale.  Everything else is that function, statement for statement.
+H264_HD void h264_gop_serial_sub(h264_gop_mb* mb, unsigned nz, bool any_cdc, bool inter, bool p_slice, h264_chain& ch, h264_mv_chain& mvc, int vx, int vy,
+                                 h264_writer& w, int* skip_run) {
+    int cbp_luma = 0;
+    if (inter) {
+        for (int i = 0; i < 4; ++i)
+            if (nz & (0xfu << (4 * i))) cbp_luma |= 1 << i;
+    } else if (nz & 0xffffu) {
+        cbp_luma = 15;
+    }
+    const int cbp_chroma = (nz & 0xff0000u) ? 2 : any_cdc ? 1 : 0;
+    const int mvdx = vx - mvc.vx, mvdy = vy - mvc.vy;
+    if (inter && !cbp_luma && !cbp_chroma && !vx && !vy) {  // P_Skip: inferred vector (0, 0), no residual
+        ++*skip_run;
+        mb->mode = kH264ModeSkip;
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 0;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 0;
+        mvc.vx = mvc.vy = 0;
+        return;
+    }
+    if (p_slice) {
+        h264_put_ue(w, (unsigned)*skip_run);            // mb_skip_run
+        *skip_run = 0;
+    }
+    uint8_t tcy[16], tcc[8];
+    h264_counter cnt;
+    cnt.bits = 0, cnt.failed = false;
+    h264_gop_code_mb_mv(mb->lev, inter, p_slice, cbp_luma, cbp_chroma, ch, mvdx, mvdy, cnt, tcy, tcc);
+    if (cnt.failed || cnt.bits > 3200) {                // Annex A.3.1 / level_prefix <= 15: I_PCM
+        h264_put_ue(w, p_slice ? 30u : 25u);
+        while (w.n) w.put(0u, 1);                       // pcm_alignment_zero_bit
+        for (int i = 0; i < 256; ++i) w.put(mb->sy[i], 8);
+        for (int i = 0; i < 128; ++i) w.put(mb->sc[i], 8);
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 16;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 16;
+        mb->mode = kH264ModePcm;
+        mvc.vx = mvc.vy = 0;
+        return;
+    }
+    h264_gop_code_mb_mv(mb->lev, inter, p_slice, cbp_luma, cbp_chroma, ch, mvdx, mvdy, w, tcy, tcc);
+    for (int i = 0; i < 4; ++i) ch.tcy[i] = tcy[i * 4 + 3];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 2; ++i) ch.tcc[c][i] = tcc[c * 4 + i * 2 + 1];
+    mb->mode = inter ? kH264ModeInter : kH264ModeIntra;
+    mvc.vx = inter ? vx : 0, mvc.vy = inter ? vy : 0;
+}
+
+// h264_gop_encode_mb_mv for a quarter-sample vector: mb->sy / sc are loaded, and in a P picture the windows wy (21 x 21) and wc (2 x 9 x 9)
+// through h264_sub_luma_at / h264_sub_chroma_at; leaves mb->ry / rc.  (Host; the kernel spreads the per-sample pieces over its lanes.)
+inline void h264_gop_encode_mb_sub(h264_gop_mb* mb, h264_chain& ch, h264_mv_chain& mvc, bool p_slice, int qp, const h264_sub_ref& at, const uint8_t* wy,
+                                   const uint8_t* wc, h264_writer& w, int* skip_run) {
+    if (p_slice) {
+        for (int i = 0; i < 256; ++i) mb->fy[i] = (uint8_t)h264_sub_pred_luma(wy, at, i & 15, i >> 4);
+        for (int i = 0; i < 128; ++i)
+            mb->fc[i] = (uint8_t)h264_sub_pred_chroma(wc + (i >> 6) * kH264SubChromaWin * kH264SubChromaWin, at, i & 7, (i >> 3) & 7);
+    }
+    h264_gop_pred(mb, ch);
+    bool inter = false;
+    if (p_slice) {
+        int si = 0, sp = 0;
+        for (int b = 0; b < 16; ++b) {
+            int a, c;
+            h264_gop_block_sad(mb, b, &a, &c);
+            si += a, sp += c;
+        }
+        inter = !(si < sp);
+    }
+    unsigned nz = 0;
+    for (int b = 0; b < 24; ++b)
+        if (h264_gop_block_forward(mb, b, inter, qp)) nz |= 1u << b;
+    const bool any_cdc = h264_gop_dc(mb, inter, qp);
+    h264_gop_serial_sub(mb, nz, any_cdc, inter, p_slice, ch, mvc, at.vx, at.vy, w, skip_run);
+    for (int b = 0; b < 24; ++b) h264_gop_block_recon(mb, b, qp);
+    h264_gop_chain(mb, ch);
+}

@@ -15,6 +15,11 @@ where nothing is left to code.  tests/h264_p_ref.py restates and decodes that st
 one vector of even whole samples, at most ``search`` luma samples a component, found by an exhaustive search on the source pictures: the
 prediction is a displaced copy in luma and chroma.  tests/h264_me_ref.py restates it.  ``search`` 0 is the code and the bytes of ``gop`` alone.
 
+``subpel`` in {1, 2, 4} (opt-in on top of ``search`` > 0; include/sdv_hip_h264_sub.h and DESIGN.md "H.264 sub-sample motion") puts the vectors on
+the grid of whole, half or quarter samples: every whole-sample vector, odd ones included, then a half- and a quarter-sample refinement, with
+the standard's 6-tap luma and bilinear chroma prediction.  tests/h264_sub_ref.py restates it.  ``subpel`` 0 is the code and the bytes of
+``search`` alone.
+
 Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
 """
 from __future__ import annotations
@@ -28,6 +33,7 @@ from . import hip
 DEFAULT_QP = 16
 DEFAULT_GOP = 1                                                                                 # a setting, not a measured optimum
 DEFAULT_SEARCH = 0                                                                              # a setting, not a measured optimum
+DEFAULT_SUBPEL = 0                                                                              # a setting, not a measured optimum
 
 
 def check_qp(qp) -> int:
@@ -48,6 +54,12 @@ def check_search(search) -> int:
     return search
 
 
+def check_subpel(subpel) -> int:
+    if isinstance(subpel, bool) or not isinstance(subpel, int) or subpel not in (0,) + hip.H264_SUBPELS:
+        raise ValueError(f"h264 subpel must be one of the integers 0, 1, 2, 4, got {subpel!r}")
+    return subpel
+
+
 class H264Encoder:
     """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
     (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.  With ``gop``
@@ -55,16 +67,19 @@ class H264Encoder:
     others are P pictures, and every call starts a new GOP.  ``return_recon=True`` returns ``(samples, (ry, rcb, rcr))``, the
     decoder's pictures as padded planes in GPU memory (they belong to the workspace: the next call overwrites them).  ``search`` > 0
     (even, at most 16; no effect with ``gop`` 1, which has no P pictures) motion-compensates the P pictures: one more launch for the
-    search over all of them, then one launch per picture position of the GOPs instead of one for all.
+    search over all of them, then one launch per picture position of the GOPs instead of one for all.  ``subpel`` 1, 2 or 4 (no
+    effect unless ``gop`` > 1 and ``search`` > 0) runs the same number of launches through the quarter-sample pair of entry points.
 
     Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
     prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
     capacity bound of sdv_hip.h, so no batch can fail to fit."""
 
-    def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH):
+    def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH,
+                 subpel: int = DEFAULT_SUBPEL):
         self.qp = check_qp(qp)
         self.gop = check_gop(gop)
         self.search = check_search(search)
+        self.subpel = check_subpel(subpel)
         self.last_sync: List[int] = []
         self.device = torch.device(device) if device is not None else None
         self._ws: Dict[tuple, dict] = {}
@@ -87,7 +102,7 @@ class H264Encoder:
                       out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True))
             if gops:                                                                            # the reference pictures stay in HBM
                 ws.update(ry=torch.empty_like(ws["y"]), rcb=torch.empty_like(ws["cb"]), rcr=torch.empty_like(ws["cr"]))
-                if self.search:
+                if self.search:                                                                 # even samples, or quarter samples with subpel
                     ws.update(mv=torch.empty((n, mbh, mbw, 2), dtype=torch.int16, device=device))
             if len(self._ws) >= 4:                                                              # a walk uses one or two shapes
                 self._ws.pop(next(iter(self._ws)))
@@ -138,6 +153,12 @@ class H264Encoder:
         elif self.search == 0:
             hip.h264_encode_gops(ws["y"], ws["cb"], ws["cr"], self.qp, self.gop, int(first_index), ws["ry"], ws["rcb"], ws["rcr"], ws["scratch"])
             hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
+        elif self.subpel:
+            hip.h264_motion_search_sub(ws["y"], self.qp, self.gop, self.search, self.subpel, ws["mv"])
+            for k in range(min(self.gop, n)):
+                hip.h264_encode_gop_step_sub(ws["y"], ws["cb"], ws["cr"], self.qp, self.gop, k, self.search, self.subpel, int(first_index), ws["mv"],
+                                             ws["ry"], ws["rcb"], ws["rcr"], ws["scratch"])
+            hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
         else:
             hip.h264_motion_search(ws["y"], self.qp, self.gop, self.search, ws["mv"])
             for k in range(min(self.gop, n)):                                                   # the kernel boundary orders picture k - 1 before k
@@ -160,9 +181,9 @@ class H264Encoder:
 _encoders: Dict[tuple, H264Encoder] = {}
 
 
-def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH) -> H264Encoder:
-    """One cached encoder (and its workspaces) per quality setting, GOP length, search range and device."""
-    key = (check_qp(qp), str(device), check_gop(gop), check_search(search))
+def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH, subpel: int = DEFAULT_SUBPEL) -> H264Encoder:
+    """One cached encoder (and its workspaces) per quality setting, GOP length, search range, vector grid and device."""
+    key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel))
     if key not in _encoders:
-        _encoders[key] = H264Encoder(qp, device, gop, search)
+        _encoders[key] = H264Encoder(qp, device, gop, search, subpel)
     return _encoders[key]

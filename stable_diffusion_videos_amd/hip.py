@@ -116,6 +116,12 @@ _EXT_SIGNATURES = {
     "sdv_h264_encode_gop_step": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 8 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
 }
 EXTENSION_SYMBOLS = tuple(_EXT_SIGNATURES)
+# include/sdv_hip_h264_sub.h: the same pair with quarter-sample vectors (one more int32, ``subpel``, after ``search``)
+_H264_SUB_SIGNATURES = {
+    "sdv_h264_motion_search_sub": (C.c_int, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p] * 3),
+    "sdv_h264_encode_gop_step_sub": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+}
+H264_SUB_SYMBOLS = tuple(_H264_SUB_SIGNATURES)
 
 
 def lib_path() -> Path:
@@ -136,7 +142,7 @@ def load(build_if_missing: bool = False):
                 f"{_LIB_PATH} is missing - build it with `python -m stable_diffusion_videos_amd.build` "
                 "(there is no CPU / eager fallback for the hot path)")
     lib = C.CDLL(str(_LIB_PATH))
-    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1680,6 +1686,95 @@ def h264_encode_gop_step(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp
     sdv_hip_ext.h; ``torch.ops.sdv.k_h264_encode_gop_step`` -> sdv_h264_encode_gop_step).  Call it for k = 0 .. min(gop, n) - 1 in order on
     one stream: picture k predicts from the reconstruction the launch before it left in ``ry`` / ``rcb`` / ``rcr``."""
     _k_h264_encode_gop_step(y, cb, cr, int(qp), int(gop), int(k), int(search), int(first_index), mv, ry, rcb, rcr, scratch)
+
+
+H264_SUBPELS = (1, 2, 4)
+
+
+def _h264_subpel_value(what, subpel):
+    if subpel not in H264_SUBPELS:
+        raise SdvHipError(f"{what}: subpel must be 1, 2 or 4, got {subpel} (0 is sdv_h264_motion_search / sdv_h264_encode_gop_step and never comes here)")
+
+
+def _h264_motion_search_sub_impl(y, qp, gop, search, subpel, mv, sad):
+    what = "h264_motion_search_sub"
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.uint8 or y.ndim != 3 or not y.is_contiguous() or y.shape[0] < 1 \
+            or y.shape[1] % 16 or y.shape[2] % 16 or not y.shape[1] or not y.shape[2]:
+        raise SdvHipError(f"{what}: y must be a contiguous uint8 [n, 16 mbh, 16 mbw] tensor, got {getattr(y, 'dtype', type(y))} "
+                          f"{tuple(getattr(y, 'shape', ()))}")
+    n, mbh, mbw = y.shape[0], y.shape[1] // 16, y.shape[2] // 16
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    _h264_search_range(what, search)
+    _h264_subpel_value(what, subpel)
+    if not isinstance(mv, torch.Tensor) or mv.dtype != torch.int16 or not mv.is_contiguous() or tuple(mv.shape) != (n, mbh, mbw, 2):
+        raise SdvHipError(f"{what}: mv must be a contiguous int16 {[n, mbh, mbw, 2]} tensor, got {getattr(mv, 'dtype', type(mv))} "
+                          f"{tuple(getattr(mv, 'shape', ()))}")
+    if sad is not None and (sad.dtype != torch.int32 or not sad.is_contiguous() or tuple(sad.shape) != (n, mbh, mbw)):
+        raise SdvHipError(f"{what}: sad must be a contiguous int32 {[n, mbh, mbw]} tensor, got {sad.dtype} {tuple(sad.shape)}")
+    lib = load()
+    args = (_ptr(y, name="y"), n, mbh, mbw, int(qp), int(gop), int(search), int(subpel), _ptr(mv, name="mv"), _ptr(sad, name="sad"))
+    _launch("h264_motion_search_sub", dict(bytes=2.0 * y.numel()),
+            lambda: _check(lib.sdv_h264_motion_search_sub(*args, _stream()), "sdv_h264_motion_search_sub"))
+
+
+_k_h264_motion_search_sub = _defop("k_h264_motion_search_sub(Tensor y, int qp, int gop, int search, int subpel, Tensor(a!) mv, Tensor(b!)? sad) -> ()",
+                                   _h264_motion_search_sub_impl)
+
+
+def h264_motion_search_sub(y: torch.Tensor, qp: int, gop: int, search: int, subpel: int, mv: torch.Tensor, sad: Optional[torch.Tensor] = None):
+    """``h264_motion_search`` on the grid of 1 / ``subpel`` samples (``subpel`` 1, 2 or 4): every whole-sample vector, then a half- and a
+    quarter-sample refinement by the rule of sdv_hip_h264_sub.h (``torch.ops.sdv.k_h264_motion_search_sub`` -> sdv_h264_motion_search_sub).
+    ``mv``: int16 ``[n, mbh, mbw, 2]`` (vx, vy) in QUARTER samples, zeros for IDR pictures; ``sad``: int32 ``[n, mbh, mbw]`` (optional)."""
+    _k_h264_motion_search_sub(y, int(qp), int(gop), int(search), int(subpel), mv, sad)
+
+
+def _h264_encode_gop_step_sub_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch):
+    what = "h264_encode_gop_step_sub"
+    n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    if not 0 <= k < min(gop, n):
+        raise SdvHipError(f"{what}: position k must be 0 .. min(gop, n) - 1 = {min(gop, n) - 1}, got {k}")
+    _h264_search_range(what, search)
+    _h264_subpel_value(what, subpel)
+    if mbw > H264_GOP_MAX_MBW:
+        raise SdvHipError(f"{what}: pictures wider than {H264_GOP_MAX_MBW} macroblocks are not coded with P pictures, got mbw={mbw}")
+    if first_index < 0:
+        raise SdvHipError(f"{what}: first_index must be >= 0, got {first_index}")
+    if not isinstance(mv, torch.Tensor) or mv.dtype != torch.int16 or not mv.is_contiguous() or tuple(mv.shape) != (n, mbh, mbw, 2):
+        raise SdvHipError(f"{what}: mv must be a contiguous int16 {[n, mbh, mbw, 2]} tensor, got {getattr(mv, 'dtype', type(mv))} "
+                          f"{tuple(getattr(mv, 'shape', ()))}")
+    _h264_u8(what, "ry", ry, y.shape)
+    _h264_u8(what, "rcb", rcb, cb.shape)
+    _h264_u8(what, "rcr", rcr, cr.shape)
+    _h264_u8(what, "scratch", scratch)
+    need = h264_gop_scratch_bytes(n, mbh, mbw)
+    if scratch.ndim != 1 or scratch.numel() < need:
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n * mbh} slices of {mbw} macroblocks need {need}")
+    lib = load()
+    args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(k), int(search), int(subpel),
+            int(first_index) & 0x7fffffff, _ptr(mv, name="mv"), _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"),
+            _ptr(scratch, name="scratch"), scratch.numel())
+    _launch("h264_encode_gop_step_sub", dict(bytes=3.0 * y.numel() / min(gop, n)),
+            lambda: _check(lib.sdv_h264_encode_gop_step_sub(*args, _stream()), "sdv_h264_encode_gop_step_sub"))
+
+
+_k_h264_encode_gop_step_sub = _defop("k_h264_encode_gop_step_sub(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int k, int search, int subpel, "
+                                     "int first_index, Tensor mv, Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch) -> ()",
+                                     _h264_encode_gop_step_sub_impl)
+
+
+def h264_encode_gop_step_sub(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, k: int, search: int, subpel: int,
+                             first_index: int, mv: torch.Tensor, ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor):
+    """``h264_encode_gop_step`` with the quarter-sample vectors ``mv`` of ``h264_motion_search_sub``: interpolated luma and chroma
+    prediction (rule of sdv_hip_h264_sub.h; ``torch.ops.sdv.k_h264_encode_gop_step_sub`` -> sdv_h264_encode_gop_step_sub).  Call it for
+    k = 0 .. min(gop, n) - 1 in order on one stream."""
+    _k_h264_encode_gop_step_sub(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch)
 
 
 def _h264_pack_impl(scratch, n, mbh, mbw, out, offsets):

@@ -1,6 +1,6 @@
 """GPU H.264 CAVLC intra encoder (h264_cavlc.H264Encoder) against the two video tracks it can stand in for, on the same box.
 
-    python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N [--search R[,R...]]]
+    python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N [--search R[,R...] [--subpel S[,S...]]]]
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -22,6 +22,11 @@ With ``--gop N --search R[,R...]`` (each R even, 0 .. 16) the tool measures moti
 comparison of the same run: encode() ms and frames/s, bytes per frame, Y-PSNR of the reconstruction of all frames, and for R > 0 the
 search kernel alone and its share of encode().  Frame sets as with ``--gop`` plus ``pan2``, the glyph frame shifted by 2 k pixels in
 picture k (``pan`` moves one sample a picture, which no even vector matches).
+With ``--gop N --search R --subpel S[,S...]`` (one R > 0; each S one of 0, 1, 2, 4) the tool measures the vector grid on top of the search
+(h264_cavlc.H264Encoder(gop=N, search=R, subpel=S)): per frame set one row per S, in the order given - S = 0 is the even whole-sample
+search, the comparison of the same run: the columns above, the search kernel alone (sdv_h264_motion_search for S = 0,
+sdv_h264_motion_search_sub otherwise) and the share of vectors with a fractional component.  Frame sets as with ``--search`` plus
+``glide``, the analytic texture of tests/h264_sub_ref.py that moves by a quarter sample a picture.
 There is no fallback: without a GPU this tool fails.
 """
 from __future__ import annotations
@@ -129,6 +134,9 @@ def measure(name: str, dev_frames: torch.Tensor, reps: int) -> dict:
 def temporal_frames(kind: str, n: int, size: int, dev) -> torch.Tensor:
     """``fade`` / ``pan`` of tests/h264_p_ref.py at n x size x size, built in GPU memory from its glyph frames."""
     import h264_ref as R
+    if kind == "glide":
+        import h264_sub_ref as S
+        return torch.from_numpy(S.glide_frames(1, n, size, size)).to(dev).contiguous()
     g = torch.from_numpy(R.make_frames("glyphs", 2, size, size)).to(dev)
     if kind in ("pan", "pan2"):
         return torch.stack([torch.roll(g[0], k * (2 if kind == "pan2" else 1), dims=1) for k in range(n)]).contiguous()
@@ -187,6 +195,35 @@ def measure_search(name: str, dev_frames: torch.Tensor, gop: int, searches, reps
     return rows
 
 
+def measure_subpel(name: str, dev_frames: torch.Tensor, gop: int, search: int, subpels, reps: int) -> list:
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    n, H, W, _ = dev_frames.shape
+    y = hip.h264_planes(dev_frames)[0]
+    rows = []
+    for subpel in subpels:
+        enc = H264Encoder(16, dev_frames.device, gop=gop, search=search, subpel=subpel)
+        ev, wall = timed(lambda: enc.encode(dev_frames), reps)
+        samples, recon = enc.encode(dev_frames, return_recon=True)
+        mse = float(((recon[0][:, :H, :W].to(torch.float64) - y[:, :H, :W].to(torch.float64)) ** 2).mean())
+        mv = torch.empty((n, y.shape[1] // 16, y.shape[2] // 16, 2), dtype=torch.int16, device=dev_frames.device)
+        if subpel:
+            ms = timed(lambda: hip.h264_motion_search_sub(y, 16, gop, search, subpel, mv), reps)[0]
+        else:
+            ms = timed(lambda: hip.h264_motion_search(y, 16, gop, search, mv), reps)[0]
+        row = dict(content=name, n=n, H=H, W=W, qp=16, gop=gop, search=search, subpel=subpel, launches=4 + min(gop, n),
+                   encode_ms_events=round(ev, 3), encode_ms_host_clock=round(wall, 3), frames_per_sec=round(n / wall * 1e3, 1),
+                   bytes_per_frame=int(sum(len(s) for s in samples) // n), y_psnr_db=round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None,
+                   search_kernel_ms=round(ms, 3), search_share_of_encode=round(ms / ev, 3),
+                   nonzero_vectors=round(float((mv != 0).any(dim=-1).float().mean()), 4),
+                   fractional_vectors=round(float((mv % 4 != 0).any(dim=-1).float().mean()), 4) if subpel else 0.0)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del enc, recon
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main_gop(args):
     from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
     from stable_diffusion_videos_amd.upsampling import RealESRGANModel
@@ -206,8 +243,14 @@ def main_gop(args):
         result["tool"] += f" --search {args.search}"
         sets.insert(3, ("pan2", lambda: temporal_frames("pan2", 128, 512, dev)))
         sets.append(("pan2", lambda: temporal_frames("pan2", 8, 2048, dev)))
+    if args.subpel is not None:
+        result["tool"] += f" --subpel {args.subpel}"
+        sets.insert(4, ("glide", lambda: temporal_frames("glide", 128, 512, dev)))
+        sets.append(("glide", lambda: temporal_frames("glide", 8, 2048, dev)))
     for name, make in sets:
-        if args.search is not None:
+        if args.subpel is not None:
+            result["rows"] += measure_subpel(name, make().contiguous(), args.gop, args.searches[0], args.subpels, args.reps)
+        elif args.search is not None:
             result["rows"] += measure_search(name, make().contiguous(), args.gop, args.searches, args.reps)
         else:
             result["rows"] += measure_gop(name, make().contiguous(), args.gop, args.reps)
@@ -225,6 +268,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--gop", type=int, default=1, help="N > 1: measure the GOP path, rows for gop 1 and gop N side by side")
     ap.add_argument("--search", default=None, help="with --gop N: R[,R...] (even, 0 .. 16): one row per motion search range, 0 = none")
+    ap.add_argument("--subpel", default=None, help="with --gop N --search R (one R > 0): S[,S...] (0, 1, 2, 4): one row per vector grid, 0 = even samples")
     args = ap.parse_args()
     if args.search is not None:
         if args.gop == 1:
@@ -232,6 +276,12 @@ def main():
         args.searches = [int(v) for v in args.search.split(",")]
         if any(v % 2 or not 0 <= v <= 16 for v in args.searches):
             raise SystemExit("--search takes even values 0 .. 16")
+    if args.subpel is not None:
+        if args.search is None or len(args.searches) != 1 or args.searches[0] == 0:
+            raise SystemExit("--subpel needs --gop N > 1 and --search R with one R > 0")
+        args.subpels = [int(v) for v in args.subpel.split(",")]
+        if any(v not in (0, 1, 2, 4) for v in args.subpels):
+            raise SystemExit("--subpel takes the values 0, 1, 2, 4")
     if not torch.cuda.is_available():
         raise SystemExit("h264_bench needs the GPU (no fallback)")
     if args.gop != 1:
