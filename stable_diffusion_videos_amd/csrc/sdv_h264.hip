@@ -11,6 +11,9 @@
 //   sdv_h264_motion_search_sub, sdv_h264_encode_gop_step_sub (sdv_hip_h264_sub.h "H.264 sub-sample motion")
 //                          the same pair with vectors in quarter samples: odd whole, half and quarter samples, 6-tap luma and bilinear
 //                          chroma prediction from clamped LDS windows
+//   sdv_h264_encode_idr4 (sdv_hip_h264_i4.h "H.264 Intra4x4")
+//                          the IDR pictures of a call with Intra4x4 prediction (I_NxN against Intra16x16 DC per macroblock), into the
+//                          GOP path's slots; the P pictures then come from one of the two step entry points above
 //   sdv_h264_pack          slots -> one contiguous buffer in sample order, and offsets[n + 1]
 //   sdv_h264_vlc_tables    host only: the VLC tables of the kernel as (length, code) pairs
 //
@@ -28,6 +31,7 @@
 #include "sdv_h264_core.h"
 #include "sdv_hip_ext.h"
 #include "sdv_hip_h264_sub.h"
+#include "sdv_hip_h264_i4.h"
 
 namespace {
 
@@ -587,6 +591,90 @@ __global__ __launch_bounds__(64) void h264_gop_step_sub_kernel(const uint8_t* __
     }
 }
 
+// Intra4x4 IDR pictures (sdv_hip_h264_i4.h "H.264 Intra4x4"): one wave per (IDR picture, macroblock row) on h264_gop_step_kernel's
+// skeleton - source staged in LDS, lane 0 keeps the serial coder, lanes 0 - 31 store the reconstruction.  The new part is the 16-step
+// block loop: lane 0 has left the block's neighbour samples in LDS (from the LDS reconstruction and the chain's column); lane 4 m + r
+// computes row r of mode m (36 lanes, 4 samples each, all through h264_i4_pred), a two-step shuffle sum gives every lane of a mode its
+// SAD, one wave minimum of h264_i4_key picks the winner for all lanes alike; lane 0 transforms, quantises and reconstructs it into LDS
+// and gathers the next block's neighbours; one barrier, in uniform control flow, ends the step.  Two waves per SIMD are asked for: left
+// alone the compiler takes 256 VGPRs + 32 AGPRs (one wave per SIMD); held to 256 it needs 237 VGPRs and spills none.
+__global__ __launch_bounds__(64, 2) void h264_idr4_kernel(const uint8_t* __restrict__ y, const uint8_t* __restrict__ cb, const uint8_t* __restrict__ cr,
+                                                       int n, int mbh, int mbw, int qp, int gop, int first_index, uint8_t* __restrict__ ry,
+                                                       uint8_t* __restrict__ rcb, uint8_t* __restrict__ rcr, uint8_t* __restrict__ slots,
+                                                       long long stride, long long slot_bytes, int32_t* __restrict__ lens) {
+    __shared__ h264_gop_mb mb;
+    __shared__ h264_i4_mb i4;
+    const int lane = threadIdx.x;
+    const int r = (int)(blockIdx.x % mbh);
+    const long long f = (long long)(blockIdx.x / mbh) * gop;
+    if (f >= n) return;
+    const long long lw = (long long)mbw * 16, cw = (long long)mbw * 8;
+    const long long row = f * mbh + r;
+    uint8_t* slot = slots + row * stride;
+    h264_writer w;
+    h264_i4_chain ch;
+    w.init(slot + 5, slot_bytes - 5);
+    ch.ch.have = 0;
+    if (lane == 0) h264_slice_header(w, (unsigned)(r * mbw), (unsigned)((first_index + f) & 1), qp);
+    const long long yat = row * 16 * lw, cat = row * 8 * cw;
+    const int lambda = h264_me_lambda(qp);
+    const int cand_mode = lane >> 2, cand_row = lane & 3;
+    for (int m = 0; m < mbw; ++m) {
+        if (lane < 16) {
+            *(uint4*)(mb.sy + lane * 16) = *(const uint4*)(y + yat + lane * lw + m * 16);
+        } else if (lane < 32) {
+            const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+            *(uint2*)(mb.sc + c * 64 + i * 8) = *(const uint2*)((c ? cr : cb) + cat + i * cw + m * 8);
+        }
+        if (lane == 0) h264_i4_begin(&mb, &i4, ch);
+        __syncthreads();
+        const int dc16 = h264_i4_dc16(h264_wave_sum(lane < 16 ? h264_i4_block_sum(&mb, lane) : 0));
+        const int sad16 = h264_wave_sum(lane < 16 ? h264_i4_block_sad16(&mb, lane, dc16) : 0);
+        for (int b = 0; b < 16; ++b) {
+            int bx, by;
+            h264_gop_block_xy(b, &bx, &by);
+            const int pm = h264_i4_pred_mode(&i4, bx >> 2, by >> 2);
+            const bool ok = cand_mode < kH264I4Modes && h264_i4_mode_ok(cand_mode, i4.avail);
+            int s = ok ? h264_i4_row_sad(&mb, &i4, b, cand_mode, cand_row) : 0;
+            s += __shfl_xor(s, 1);
+            s += __shfl_xor(s, 2);
+            unsigned key = ok ? h264_i4_key(s, lambda, cand_mode, pm) : 0xffffffffu;       // DC is always admitted, so there is a winner
+#pragma unroll
+            for (int o = 32; o; o >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, o));
+            if (lane == 0) h264_i4_block_code(&mb, &i4, b, key, qp);
+            __syncthreads();
+        }
+        const bool use_i4 = i4.cost < sad16;
+        const bool mine = lane < 24 && (lane >= 16 || !use_i4) && h264_gop_block_forward(&mb, lane, false, qp);
+        const unsigned nz = (unsigned)__ballot(mine);
+        __syncthreads();
+        if (lane == 0) {
+            const bool any_cdc = h264_gop_dc(&mb, false, qp);
+            h264_i4_serial(&mb, &i4, use_i4, nz, any_cdc, ch, w);
+        }
+        __syncthreads();
+        if (lane < 24) h264_i4_block_recon(&mb, lane, qp);
+        __syncthreads();
+        if (lane < 16) {
+            *(uint4*)(ry + yat + lane * lw + m * 16) = *(const uint4*)(mb.ry + lane * 16);
+        } else if (lane < 32) {
+            const int c = (lane - 16) >> 3, i = (lane - 16) & 7;
+            *(uint2*)((c ? rcr : rcb) + cat + i * cw + m * 8) = *(const uint2*)(mb.rc + c * 64 + i * 8);
+        }
+        if (lane == 0) h264_gop_chain(&mb, ch.ch);
+        __syncthreads();
+    }
+    if (lane == 0) {
+        w.put(1u, 1);                                   // rbsp_slice_trailing_bits
+        while (w.n) w.put(0u, 1);
+        const long long used = min(w.pos, slot_bytes - 5);      // (the capacity bound keeps pos below it; nothing was stored beyond)
+        const unsigned len = (unsigned)(1 + used);
+        slot[0] = (uint8_t)(len >> 24), slot[1] = (uint8_t)(len >> 16), slot[2] = (uint8_t)(len >> 8), slot[3] = (uint8_t)len;
+        slot[4] = 0x65;                                 // nal_ref_idc 3, nal_unit_type 5
+        lens[row] = (int32_t)(5 + used);
+    }
+}
+
 struct h264_layout {
     long long rows, slot, stride, starts_at, lens_at, bytes;
 };
@@ -756,6 +844,31 @@ extern "C" int sdv_h264_encode_gop_step_sub(const uint8_t* y, const uint8_t* cb,
     hipLaunchKernelGGL(h264_gop_step_sub_kernel, dim3((unsigned)chains), dim3(64), 0, (hipStream_t)stream, y, cb, cr, n, mbh, mbw, qp, gop, k, search,
                        subpel, first_index, mv, ry, rcb, rcr, base, l.stride, l.slot, (int32_t*)(base + l.lens_at));
     SDV_CHECK_LAUNCH("sdv_h264_encode_gop_step_sub");
+    return SDV_OK;
+}
+
+// ---- Intra4x4 IDR pictures (include/sdv_hip_h264_i4.h): the pictures at positions k % gop == 0 of a call, into the GOP path's slots ----
+extern "C" int sdv_h264_encode_idr4(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, int32_t n, int32_t mbh, int32_t mbw, int32_t qp,
+                                    int32_t gop, int32_t first_index, uint8_t* ry, uint8_t* rcb, uint8_t* rcr, void* scratch,
+                                    int64_t scratch_bytes, void* stream) {
+    SDV_REQUIRE(y && cb && cr && ry && rcb && rcr && scratch, "sdv_h264_encode_idr4: null pointer");
+    H264_GRID_ARGS("sdv_h264_encode_idr4");
+    SDV_REQUIRE(mbw <= 1008, "sdv_h264_encode_idr4: mbw=%d above 1008 (its slots are those of a wider picture, which must stay within 1024)", mbw);
+    SDV_REQUIRE(qp >= 0 && qp <= 51, "sdv_h264_encode_idr4: qp=%d outside 0 .. 51", qp);
+    SDV_REQUIRE(gop >= 1 && gop <= kH264GopMax, "sdv_h264_encode_idr4: gop=%d outside 1 .. %d", gop, (int)kH264GopMax);
+    SDV_REQUIRE(first_index >= 0, "sdv_h264_encode_idr4: negative first_index");
+    const h264_layout l = h264_scratch_layout(n, mbh, h264_gop_slot_mbw(mbw));
+    SDV_REQUIRE(scratch_bytes >= l.bytes, "sdv_h264_encode_idr4: scratch buffer too small: %lld bytes, %lld slices of %d macroblocks need %lld",
+                (long long)scratch_bytes, l.rows, mbw, l.bytes);
+    SDV_REQUIRE((((uintptr_t)y) & 15) == 0 && (((uintptr_t)cb) & 7) == 0 && (((uintptr_t)cr) & 7) == 0 && (((uintptr_t)scratch) & 7) == 0,
+                "sdv_h264_encode_idr4: y must be 16-byte, cb / cr / scratch 8-byte aligned");
+    SDV_REQUIRE((((uintptr_t)ry) & 15) == 0 && (((uintptr_t)rcb) & 7) == 0 && (((uintptr_t)rcr) & 7) == 0,
+                "sdv_h264_encode_idr4: ry must be 16-byte, rcb / rcr 8-byte aligned");
+    uint8_t* base = (uint8_t*)scratch;
+    const long long chains = (long long)((n + gop - 1) / gop) * mbh;               // the IDR pictures of the call
+    hipLaunchKernelGGL(h264_idr4_kernel, dim3((unsigned)chains), dim3(64), 0, (hipStream_t)stream, y, cb, cr, n, mbh, mbw, qp, gop, first_index, ry, rcb,
+                       rcr, base, l.stride, l.slot, (int32_t*)(base + l.lens_at));
+    SDV_CHECK_LAUNCH("sdv_h264_encode_idr4");
     return SDV_OK;
 }
 

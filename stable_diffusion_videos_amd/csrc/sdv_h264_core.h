@@ -1038,3 +1038,307 @@ inline void h264_gop_encode_mb_sub(h264_gop_mb* mb, h264_chain& ch, h264_mv_chai
     for (int b = 0; b < 24; ++b) h264_gop_block_recon(mb, b, qp);
     h264_gop_chain(mb, ch);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Intra4x4 prediction for IDR pictures (sdv_hip_h264_i4.h "H.264 Intra4x4"): per macroblock I_NxN with nine modes per 4x4 block against
+// today's Intra16x16 DC, I_PCM by today's two triggers.  The sixteen blocks of a macroblock are a serial chain (each predicts from the
+// reconstruction of the ones before it), so the pieces below are per block: the neighbour samples of a block gathered into one edge
+// array, ONE predictor that kernel, host and nothing else read them through, the winner's transform / quantisation / reconstruction,
+// and the serial coder.  The kernel spreads a block's (mode, row) candidates over its lanes; h264_i4_encode_mb runs everything in
+// order on the host.  Chroma, the Intra16x16 candidate and the I_PCM writing are the GOP path's functions.  Nothing above is touched.
+// ------------------------------------------------------------------------------------------------------------------------------------
+enum { kH264ModeI4 = 4 };                               // h264_gop_mb::mode of an I_NxN macroblock (its chroma is that of kH264ModeIntra)
+enum { kH264I4Top = 1, kH264I4Left = 2, kH264I4Corner = 4, kH264I4TopRight = 8 };
+enum { kH264I4Modes = 9, kH264I4Dc = 2 };
+
+// coded_block_pattern -> codeNum of me(v), intra column of Table 9-4 (ChromaArrayType 1): the inverse of
+// 47 31 15 0 23 27 29 30 7 11 13 14 39 43 45 46 16 3 5 10 12 19 21 26 28 35 37 42 44 1 2 4 8 17 18 20 24 6 9 22 25 32 33 34 36 40 38 41
+H264_HD int h264_cbp_intra_code(int cbp) {
+    const uint8_t t[48] = {3,  29, 30, 17, 31, 18, 37, 8,  32, 38, 19, 9,  20, 10, 11, 2,  16, 33, 34, 21, 35, 22, 39, 4,
+                           36, 40, 23, 5,  24, 6,  7,  1,  41, 42, 43, 25, 44, 26, 46, 12, 45, 47, 27, 13, 28, 14, 15, 0};
+    return t[cbp];
+}
+
+// What a macroblock of an IDR picture hands to its right neighbour: the GOP path's chain plus the Intra4x4PredMode of its four right-hand
+// blocks (2 when it was coded Intra16x16 or I_PCM).
+struct h264_i4_chain {
+    h264_chain ch;
+    uint8_t mode[4];
+};
+
+// The Intra4x4 state of one macroblock that the pieces share (LDS in the kernel), beside its h264_gop_mb.
+struct h264_i4_mb {
+    uint8_t edge[16];                                   // the current block's neighbours: [0] p[-1,-1], [1 + x] p[x,-1] (x 0..7), [9 + y] p[-1,y]
+    uint8_t lcol[16], lmode[4];                         // the left neighbour's right column and right-hand modes (the chain)
+    uint8_t mode[16];                                   // the winners so far, [by * 4 + bx]
+    uint8_t pmode[16];                                  // the predicted mode of every block, [luma4x4BlkIdx]
+    int avail;                                          // kH264I4* of the current block
+    int have;                                           // a left neighbour exists
+    int cost;                                           // sum of the winners' costs
+    unsigned nz;                                        // bit b: block b (luma4x4BlkIdx) has a nonzero level
+};
+
+// Which neighbours 4x4 block (bx, by) has: the row above the macroblock is another slice, so "top" needs by >= 1.
+H264_HD int h264_i4_avail(int bx, int by, bool have_left) {
+    const bool top = by >= 1, left = bx >= 1 || have_left;
+    const bool tr = top && bx <= 2 && !(bx == 1 && (by == 1 || by == 3));
+    return (top ? kH264I4Top : 0) | (left ? kH264I4Left : 0) | (top && left ? kH264I4Corner : 0) | (tr ? kH264I4TopRight : 0);
+}
+// V, DDL, VL need top; H, HU left; DDR, VR, HD top, left and corner; DC nothing.
+H264_HD bool h264_i4_mode_ok(int mode, int avail) {
+    const uint8_t need[kH264I4Modes] = {1, 2, 0, 1, 7, 7, 7, 1, 2};
+    return (avail & need[mode]) == need[mode];
+}
+
+// serial: the neighbours of block b from the macroblock's reconstruction so far and the chain's left column, never from HBM.  Top-right
+// samples that are not available repeat p[3,-1] (8.3.1.2); samples of a missing side are 128 and read by no admitted mode but DC's sums,
+// which skip them.
+H264_HD void h264_i4_edges(const uint8_t* ry, h264_i4_mb* s, int b) {
+    int x0, y0;
+    h264_gop_block_xy(b, &x0, &y0);
+    const int avail = h264_i4_avail(x0 >> 2, y0 >> 2, s->have != 0);
+    s->avail = avail;
+    for (int i = 0; i < 13; ++i) s->edge[i] = 128;
+    if (avail & kH264I4Top) {
+        for (int i = 0; i < 4; ++i) s->edge[1 + i] = ry[(y0 - 1) * 16 + x0 + i];
+        for (int i = 4; i < 8; ++i) s->edge[1 + i] = (avail & kH264I4TopRight) ? ry[(y0 - 1) * 16 + x0 + i] : s->edge[4];
+    }
+    if (avail & kH264I4Left)
+        for (int i = 0; i < 4; ++i) s->edge[9 + i] = x0 ? ry[(y0 + i) * 16 + x0 - 1] : s->lcol[y0 + i];
+    if (avail & kH264I4Corner) s->edge[0] = x0 ? ry[(y0 - 1) * 16 + x0 - 1] : s->lcol[y0 - 1];
+}
+
+// THE predictor (8.3.1.2.1 - 8.3.1.2.9): sample (x, y) of the block in `mode` from an edge array.  p[i,-1] = t(i), i = -1 .. 7;
+// p[-1,j] = l(j), j = -1 .. 3; both reach the corner at -1.
+H264_HD int h264_i4_t(const uint8_t* e, int i) { return e[1 + i]; }
+H264_HD int h264_i4_l(const uint8_t* e, int j) { return j < 0 ? e[0] : e[9 + j]; }
+H264_HD int h264_i4_f3(int a, int b, int c) { return (a + 2 * b + c + 2) >> 2; }
+H264_HD int h264_i4_pred(const uint8_t* e, int avail, int mode, int x, int y) {
+    switch (mode) {
+    case 0: return h264_i4_t(e, x);
+    case 1: return h264_i4_l(e, y);
+    case 2: {
+        const int st = e[1] + e[2] + e[3] + e[4], sl = e[9] + e[10] + e[11] + e[12];
+        const bool top = (avail & kH264I4Top) != 0, left = (avail & kH264I4Left) != 0;
+        return top && left ? (st + sl + 4) >> 3 : top ? (st + 2) >> 2 : left ? (sl + 2) >> 2 : 128;
+    }
+    case 3:
+        if (x == 3 && y == 3) return (h264_i4_t(e, 6) + 3 * h264_i4_t(e, 7) + 2) >> 2;
+        return h264_i4_f3(h264_i4_t(e, x + y), h264_i4_t(e, x + y + 1), h264_i4_t(e, x + y + 2));
+    case 4:
+        if (x > y) return h264_i4_f3(h264_i4_t(e, x - y - 2), h264_i4_t(e, x - y - 1), h264_i4_t(e, x - y));
+        if (x < y) return h264_i4_f3(h264_i4_l(e, y - x - 2), h264_i4_l(e, y - x - 1), h264_i4_l(e, y - x));
+        return h264_i4_f3(h264_i4_t(e, 0), e[0], h264_i4_l(e, 0));
+    case 5: {
+        const int z = 2 * x - y, i = x - (y >> 1);
+        if (z >= 0 && !(z & 1)) return (h264_i4_t(e, i - 1) + h264_i4_t(e, i) + 1) >> 1;
+        if (z > 0) return h264_i4_f3(h264_i4_t(e, i - 2), h264_i4_t(e, i - 1), h264_i4_t(e, i));
+        if (z == -1) return h264_i4_f3(h264_i4_l(e, 0), e[0], h264_i4_t(e, 0));
+        return h264_i4_f3(h264_i4_l(e, y - 1), h264_i4_l(e, y - 2), h264_i4_l(e, y - 3));
+    }
+    case 6: {
+        const int z = 2 * y - x, j = y - (x >> 1);
+        if (z >= 0 && !(z & 1)) return (h264_i4_l(e, j - 1) + h264_i4_l(e, j) + 1) >> 1;
+        if (z > 0) return h264_i4_f3(h264_i4_l(e, j - 2), h264_i4_l(e, j - 1), h264_i4_l(e, j));
+        if (z == -1) return h264_i4_f3(h264_i4_l(e, 0), e[0], h264_i4_t(e, 0));
+        return h264_i4_f3(h264_i4_t(e, x - 1), h264_i4_t(e, x - 2), h264_i4_t(e, x - 3));
+    }
+    case 7: {
+        const int i = x + (y >> 1);
+        if (!(y & 1)) return (h264_i4_t(e, i) + h264_i4_t(e, i + 1) + 1) >> 1;
+        return h264_i4_f3(h264_i4_t(e, i), h264_i4_t(e, i + 1), h264_i4_t(e, i + 2));
+    }
+    default: {
+        const int z = x + 2 * y, j = y + (x >> 1);
+        if (z > 5) return h264_i4_l(e, 3);
+        if (z == 5) return (h264_i4_l(e, 2) + 3 * h264_i4_l(e, 3) + 2) >> 2;
+        if (!(z & 1)) return (h264_i4_l(e, j) + h264_i4_l(e, j + 1) + 1) >> 1;
+        return h264_i4_f3(h264_i4_l(e, j), h264_i4_l(e, j + 1), h264_i4_l(e, j + 2));
+    }
+    }
+}
+
+// predIntra4x4PredMode of block (bx, by) (8.3.1.1): min(left, top), 2 when either is missing; an Intra16x16 / I_PCM neighbour counts as 2
+// (the chain says so).  The block above the macroblock's top row is another slice, so the top row always predicts 2.
+H264_HD int h264_i4_pred_mode(const h264_i4_mb* s, int bx, int by) {
+    const int a = bx ? s->mode[by * 4 + bx - 1] : s->have ? s->lmode[by] : -1;
+    const int t = by ? s->mode[(by - 1) * 4 + bx] : -1;
+    return (a < 0 || t < 0) ? kH264I4Dc : a < t ? a : t;
+}
+// cost = SAD + lambda * (1 if the mode is the predicted one else 4), and the order (cost, mode) as one word (cost < 2^13)
+H264_HD unsigned h264_i4_key(int sad, int lambda, int mode, int pmode) { return ((unsigned)(sad + lambda * (mode == pmode ? 1 : 4)) << 4) | (unsigned)mode; }
+
+// serial: the state at the start of a macroblock - the Intra16x16 / chroma DC predictors, the chain's column and modes, block 0's edges
+H264_HD void h264_i4_begin(h264_gop_mb* mb, h264_i4_mb* s, const h264_i4_chain& ch) {
+    h264_gop_pred(mb, ch.ch);
+    s->have = ch.ch.have;
+    for (int i = 0; i < 16; ++i) s->lcol[i] = ch.ch.have ? ch.ch.ycol[i] : 128;
+    for (int i = 0; i < 4; ++i) s->lmode[i] = ch.ch.have ? ch.mode[i] : kH264I4Dc;
+    for (int i = 0; i < 16; ++i) s->mode[i] = s->pmode[i] = kH264I4Dc;
+    s->cost = 0, s->nz = 0;
+    h264_i4_edges(mb->ry, s, 0);
+}
+// The Intra16x16 candidate's cost: sum |src - DC16|, DC16 the macroblock's own DC - the rounded mean of its 256 source samples.  (What the
+// left neighbour's column mispredicts of that mean goes into the one Intra16x16 DC level, not into sixteen blocks; measured against the
+// predictor instead, a flat macroblock without a left neighbour would pay its offset from 128 sixteen times and turn I_NxN.)
+// per luma block: its part of the sum of the samples, and of the SAD against dc16 = h264_i4_dc16(sum of the sums)
+H264_HD int h264_i4_block_sum(const h264_gop_mb* mb, int b) {
+    int x, y, sum = 0;
+    h264_gop_block_xy(b, &x, &y);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) sum += mb->sy[(y + i) * 16 + x + j];
+    return sum;
+}
+H264_HD int h264_i4_dc16(int sum) { return (sum + 128) >> 8; }
+H264_HD int h264_i4_block_sad16(const h264_gop_mb* mb, int b, int dc16) {
+    int x, y, sum = 0;
+    h264_gop_block_xy(b, &x, &y);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const int d = (int)mb->sy[(y + i) * 16 + x + j] - dc16;
+            sum += d < 0 ? -d : d;
+        }
+    return sum;
+}
+// one row of one candidate: SAD of the 4 samples of row `row` of block b against mode `mode` (the kernel's lanes own one each)
+H264_HD int h264_i4_row_sad(const h264_gop_mb* mb, const h264_i4_mb* s, int b, int mode, int row) {
+    int x, y, sum = 0;
+    h264_gop_block_xy(b, &x, &y);
+    for (int j = 0; j < 4; ++j) {
+        const int d = (int)mb->sy[(y + row) * 16 + x + j] - h264_i4_pred(s->edge, s->avail, mode, j, row);
+        sum += d < 0 ? -d : d;
+    }
+    return sum;
+}
+// serial: the winner of block b (key = h264_i4_key of the minimum) - prediction, residual, transform, quantisation with the intra dead
+// zone, all 16 levels to lev block 1 + b (scan order), dequantisation, reconstruction into mb->ry; then the edges of block b + 1.
+H264_HD void h264_i4_block_code(h264_gop_mb* mb, h264_i4_mb* s, int b, unsigned key, int qp) {
+    int x0, y0, pr[16], xs[16], w[16], d[16], r[16];
+    h264_gop_block_xy(b, &x0, &y0);
+    const int mode = (int)(key & 15u);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            pr[i * 4 + j] = h264_i4_pred(s->edge, s->avail, mode, j, i);
+            xs[i * 4 + j] = (int)mb->sy[(y0 + i) * 16 + x0 + j] - pr[i * 4 + j];
+        }
+    h264_forward4x4(xs, w);
+    const int q6 = qp % 6, k = qp / 6, qbits = 15 + k, f = (1 << qbits) / 3;
+    int16_t* lv = mb->lev + (1 + b) * 16;
+    bool any = false;
+    for (int ras = 0; ras < 16; ++ras) {
+        const int cls = h264_pos_class(ras >> 2, ras & 3);
+        const int l = h264_quant(w[ras], h264_mf(q6, cls), f, qbits);
+        lv[h264_scan_pos(ras)] = (int16_t)l;
+        d[ras] = l * h264_norm(q6, cls) * (1 << k);
+        if (l) any = true;
+    }
+    mb->dcw[b] = w[0];
+    h264_inverse4x4(d, r);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) mb->ry[(y0 + i) * 16 + x0 + j] = (uint8_t)h264_clip255(pr[i * 4 + j] + r[i * 4 + j]);
+    s->pmode[b] = (uint8_t)h264_i4_pred_mode(s, x0 >> 2, y0 >> 2);
+    s->mode[(y0 >> 2) * 4 + (x0 >> 2)] = (uint8_t)mode;
+    s->cost += (int)(key >> 4);
+    if (any) s->nz |= 1u << b;
+    if (b < 15) h264_i4_edges(mb->ry, s, b + 1);
+}
+
+// macroblock_layer() of an I_NxN macroblock: mb_type, the sixteen mode symbols, chroma mode, cbp by the intra column, the residual
+template <class Sink>
+H264_HD void h264_i4_code_mb(const int16_t* lev, const h264_i4_mb* s, int cbp_luma, int cbp_chroma, const h264_chain& left, Sink& sk, uint8_t* tcy,
+                             uint8_t* tcc) {
+    for (int i = 0; i < 16; ++i) tcy[i] = 0;            // [by * 4 + bx]
+    for (int i = 0; i < 8; ++i) tcc[i] = 0;             // [c * 4 + by * 2 + bx]
+    h264_put_ue(sk, 0u);                                // mb_type I_NxN (no transform_size_8x8_flag: the PPS has no 8x8 transform)
+    for (int b = 0; b < 16; ++b) {
+        const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+        const int mode = s->mode[by * 4 + bx], pm = s->pmode[b];
+        if (mode == pm) sk.put(1u, 1);                  // prev_intra4x4_pred_mode_flag
+        else sk.put(0u, 1), sk.put((unsigned)(mode < pm ? mode : mode - 1), 3);     // rem_intra4x4_pred_mode
+    }
+    h264_put_ue(sk, 0u);                                // intra_chroma_pred_mode: DC
+    h264_put_ue(sk, (unsigned)h264_cbp_intra_code(cbp_luma + 16 * cbp_chroma));
+    if (cbp_luma || cbp_chroma) h264_put_se(sk, 0);     // mb_qp_delta
+    for (int b = 0; b < 16; ++b) {
+        if (!((cbp_luma >> (b >> 2)) & 1)) continue;
+        const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+        const int a = bx ? tcy[by * 4 + bx - 1] : left.have ? left.tcy[by] : -1;
+        const int t = by ? tcy[(by - 1) * 4 + bx] : -1;
+        tcy[by * 4 + bx] = (uint8_t)h264_code_block(lev + (1 + b) * 16, 16, h264_nc(a, t), sk);
+    }
+    h264_gop_code_chroma(lev, cbp_chroma, left, sk, tcc);
+}
+
+// serial: after the sixteen blocks and the chroma levels - the decision I_NxN against Intra16x16 (use_i4: sum of costs < SAD against the
+// macroblock's DC; otherwise the caller left the Intra16x16 levels in place), the counting pass, the I_PCM decision, the bits; leaves mb->mode and the
+// chain's TotalCoeffs and modes.  nz: the ballot of h264_gop_block_forward (luma bits only when !use_i4).
+H264_HD void h264_i4_serial(h264_gop_mb* mb, const h264_i4_mb* s, bool use_i4, unsigned nz, bool any_cdc, h264_i4_chain& ch, h264_writer& w) {
+    for (int i = 0; i < 4; ++i) ch.mode[i] = kH264I4Dc;
+    if (!use_i4) {
+        int skip_run = 0;
+        h264_gop_serial(mb, nz, any_cdc, false, false, ch.ch, w, &skip_run);
+        return;
+    }
+    int cbp_luma = 0;
+    for (int i = 0; i < 4; ++i)
+        if (s->nz & (0xfu << (4 * i))) cbp_luma |= 1 << i;
+    const int cbp_chroma = (nz & 0xff0000u) ? 2 : any_cdc ? 1 : 0;
+    uint8_t tcy[16], tcc[8];
+    h264_counter cnt;
+    cnt.bits = 0, cnt.failed = false;
+    h264_i4_code_mb(mb->lev, s, cbp_luma, cbp_chroma, ch.ch, cnt, tcy, tcc);
+    if (cnt.failed || cnt.bits > 3200) {                // Annex A.3.1 / level_prefix <= 15: I_PCM
+        h264_put_ue(w, 25u);
+        while (w.n) w.put(0u, 1);                       // pcm_alignment_zero_bit
+        for (int i = 0; i < 256; ++i) w.put(mb->sy[i], 8);
+        for (int i = 0; i < 128; ++i) w.put(mb->sc[i], 8);
+        for (int i = 0; i < 4; ++i) ch.ch.tcy[i] = 16;
+        ch.ch.tcc[0][0] = ch.ch.tcc[0][1] = ch.ch.tcc[1][0] = ch.ch.tcc[1][1] = 16;
+        mb->mode = kH264ModePcm;
+        return;
+    }
+    h264_i4_code_mb(mb->lev, s, cbp_luma, cbp_chroma, ch.ch, w, tcy, tcc);
+    for (int i = 0; i < 4; ++i) ch.ch.tcy[i] = tcy[i * 4 + 3];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 2; ++i) ch.ch.tcc[c][i] = tcc[c * 4 + i * 2 + 1];
+    for (int i = 0; i < 4; ++i) ch.mode[i] = s->mode[i * 4 + 3];
+    mb->mode = kH264ModeI4;
+}
+// per block: reconstruction after the serial part - an I_NxN macroblock's luma already stands in mb->ry
+H264_HD void h264_i4_block_recon(h264_gop_mb* mb, int b, int qp) {
+    if (mb->mode == kH264ModeI4 && b < 16) return;
+    h264_gop_block_recon(mb, b, qp);
+}
+
+// The whole macroblock step of an IDR picture in order (host; the kernel spreads the candidates and the per-block pieces over its lanes).
+// mb->sy / sc are loaded; leaves mb->ry / rc.  Returns mb->mode.
+inline int h264_i4_encode_mb(h264_gop_mb* mb, h264_i4_mb* s, h264_i4_chain& ch, int qp, h264_writer& w) {
+    h264_i4_begin(mb, s, ch);
+    const int lambda = h264_me_lambda(qp);
+    int sum = 0, sad16 = 0;
+    for (int b = 0; b < 16; ++b) sum += h264_i4_block_sum(mb, b);
+    for (int b = 0; b < 16; ++b) sad16 += h264_i4_block_sad16(mb, b, h264_i4_dc16(sum));
+    for (int b = 0; b < 16; ++b) {
+        int x, y;
+        h264_gop_block_xy(b, &x, &y);
+        const int pm = h264_i4_pred_mode(s, x >> 2, y >> 2);
+        unsigned best = 0xffffffffu;
+        for (int mode = 0; mode < kH264I4Modes; ++mode) {
+            if (!h264_i4_mode_ok(mode, s->avail)) continue;
+            int sad = 0;
+            for (int row = 0; row < 4; ++row) sad += h264_i4_row_sad(mb, s, b, mode, row);
+            const unsigned key = h264_i4_key(sad, lambda, mode, pm);
+            if (key < best) best = key;
+        }
+        h264_i4_block_code(mb, s, b, best, qp);
+    }
+    const bool use_i4 = s->cost < sad16;
+    unsigned nz = 0;
+    for (int b = use_i4 ? 16 : 0; b < 24; ++b)
+        if (h264_gop_block_forward(mb, b, false, qp)) nz |= 1u << b;
+    const bool any_cdc = h264_gop_dc(mb, false, qp);
+    h264_i4_serial(mb, s, use_i4, nz, any_cdc, ch, w);
+    for (int b = 0; b < 24; ++b) h264_i4_block_recon(mb, b, qp);
+    h264_gop_chain(mb, ch.ch);
+    return mb->mode;
+}

@@ -20,6 +20,11 @@ the grid of whole, half or quarter samples: every whole-sample vector, odd ones 
 the standard's 6-tap luma and bilinear chroma prediction.  tests/h264_sub_ref.py restates it.  ``subpel`` 0 is the code and the bytes of
 ``search`` alone.
 
+``intra4`` 1 (opt-in, at any ``gop``; include/sdv_hip_h264_i4.h and DESIGN.md "H.264 Intra4x4") codes every IDR picture of a call with a
+kernel of its own that chooses per macroblock between ``I_NxN`` (Intra4x4 prediction, nine modes per 4x4 block) and the Intra16x16 DC
+macroblock above; P pictures are untouched.  tests/h264_i4_ref.py restates and decodes it.  ``intra4`` 0 is the code and the bytes of
+the other settings alone.
+
 Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
 """
 from __future__ import annotations
@@ -34,6 +39,7 @@ DEFAULT_QP = 16
 DEFAULT_GOP = 1                                                                                 # a setting, not a measured optimum
 DEFAULT_SEARCH = 0                                                                              # a setting, not a measured optimum
 DEFAULT_SUBPEL = 0                                                                              # a setting, not a measured optimum
+DEFAULT_INTRA4 = 0                                                                              # a setting, not a measured optimum
 
 
 def check_qp(qp) -> int:
@@ -60,6 +66,12 @@ def check_subpel(subpel) -> int:
     return subpel
 
 
+def check_intra4(intra4) -> int:
+    if isinstance(intra4, bool) or not isinstance(intra4, int) or intra4 not in (0, 1):
+        raise ValueError(f"h264 intra4 must be one of the integers 0, 1, got {intra4!r}")
+    return intra4
+
+
 class H264Encoder:
     """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
     (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.  With ``gop``
@@ -69,17 +81,21 @@ class H264Encoder:
     (even, at most 16; no effect with ``gop`` 1, which has no P pictures) motion-compensates the P pictures: one more launch for the
     search over all of them, then one launch per picture position of the GOPs instead of one for all.  ``subpel`` 1, 2 or 4 (no
     effect unless ``gop`` > 1 and ``search`` > 0) runs the same number of launches through the quarter-sample pair of entry points.
+    ``intra4`` 1 codes the IDR pictures with Intra4x4 prediction: one launch for all of them, then one launch per P picture position
+    (always the per-position entry points, with zero vectors when ``search`` is 0); the workspaces are then those of the GOP path at
+    any ``gop``, so ``return_recon`` works at ``gop`` 1 too.
 
     Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
     prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
     capacity bound of sdv_hip.h, so no batch can fail to fit."""
 
     def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH,
-                 subpel: int = DEFAULT_SUBPEL):
+                 subpel: int = DEFAULT_SUBPEL, intra4: int = DEFAULT_INTRA4):
         self.qp = check_qp(qp)
         self.gop = check_gop(gop)
         self.search = check_search(search)
         self.subpel = check_subpel(subpel)
+        self.intra4 = check_intra4(intra4)
         self.last_sync: List[int] = []
         self.device = torch.device(device) if device is not None else None
         self._ws: Dict[tuple, dict] = {}
@@ -89,7 +105,7 @@ class H264Encoder:
         key = (n, mbh, mbw, str(device))
         ws = self._ws.get(key)
         if ws is None:
-            gops = self.gop > 1
+            gops = self.gop > 1 or self.intra4 == 1                                          # Intra4x4 uses the GOP slots at any gop
             cap = hip.h264_gop_out_bytes(n, mbh, mbw) if gops else hip.h264_out_bytes(n, mbh, mbw)
             scratch = hip.h264_gop_scratch_bytes(n, mbh, mbw) if gops else hip.h264_scratch_bytes(n, mbh, mbw)
             ws = dict(y=torch.empty((n, 16 * mbh, 16 * mbw), dtype=torch.uint8, device=device),
@@ -102,8 +118,10 @@ class H264Encoder:
                       out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True))
             if gops:                                                                            # the reference pictures stay in HBM
                 ws.update(ry=torch.empty_like(ws["y"]), rcb=torch.empty_like(ws["cb"]), rcr=torch.empty_like(ws["cr"]))
-                if self.search:                                                                 # even samples, or quarter samples with subpel
+                if self.search and self.gop > 1:                                                # even samples, or quarter samples with subpel
                     ws.update(mv=torch.empty((n, mbh, mbw, 2), dtype=torch.int16, device=device))
+                elif self.intra4 and self.gop > 1:                                              # zero vectors for the per-position entry point
+                    ws.update(mv=torch.zeros((n, mbh, mbw, 2), dtype=torch.int16, device=device))
             if len(self._ws) >= 4:                                                              # a walk uses one or two shapes
                 self._ws.pop(next(iter(self._ws)))
             self._ws[key] = ws
@@ -145,7 +163,10 @@ class H264Encoder:
             return self._rows_and_pack(ws, n, mbh, mbw, first_index, return_recon)
 
     def _rows_and_pack(self, ws: dict, n: int, mbh: int, mbw: int, first_index: int, return_recon: bool = False):
-        if self.gop == 1:
+        if self.intra4:
+            self._idr4_and_steps(ws, n, int(first_index))
+            hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
+        elif self.gop == 1:
             if return_recon:
                 raise hip.SdvHipError("H264Encoder: the all-intra path (gop 1) reconstructs only what its chains read; return_recon needs gop > 1")
             hip.h264_encode_rows(ws["y"], ws["cb"], ws["cr"], self.qp, int(first_index), ws["scratch"])
@@ -178,12 +199,31 @@ class H264Encoder:
         return (samples, (ws["ry"], ws["rcb"], ws["rcr"])) if return_recon else samples
 
 
+    def _idr4_and_steps(self, ws: dict, n: int, first_index: int):
+        """``intra4``: the IDR pictures of the call in one launch, then the P picture positions in order (the kernel boundaries order
+        picture k - 1 before k).  Without a search the P pictures take the whole-sample entry point with its smallest range and zero
+        vectors, which is the zero-motion prediction of ``gop`` alone."""
+        planes, recon = (ws["y"], ws["cb"], ws["cr"]), (ws["ry"], ws["rcb"], ws["rcr"])
+        steps = range(1, min(self.gop, n))
+        if steps and self.search and self.subpel:
+            hip.h264_motion_search_sub(ws["y"], self.qp, self.gop, self.search, self.subpel, ws["mv"])
+        elif steps and self.search:
+            hip.h264_motion_search(ws["y"], self.qp, self.gop, self.search, ws["mv"])
+        hip.h264_encode_idr4(*planes, self.qp, self.gop, first_index, *recon, ws["scratch"])
+        for k in steps:
+            if self.search and self.subpel:
+                hip.h264_encode_gop_step_sub(*planes, self.qp, self.gop, k, self.search, self.subpel, first_index, ws["mv"], *recon, ws["scratch"])
+            else:
+                hip.h264_encode_gop_step(*planes, self.qp, self.gop, k, self.search or 2, first_index, ws["mv"], *recon, ws["scratch"])
+
+
 _encoders: Dict[tuple, H264Encoder] = {}
 
 
-def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH, subpel: int = DEFAULT_SUBPEL) -> H264Encoder:
-    """One cached encoder (and its workspaces) per quality setting, GOP length, search range, vector grid and device."""
-    key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel))
+def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH, subpel: int = DEFAULT_SUBPEL,
+                intra4: int = DEFAULT_INTRA4) -> H264Encoder:
+    """One cached encoder (and its workspaces) per quality setting, GOP length, search range, vector grid, intra setting and device."""
+    key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel), check_intra4(intra4))
     if key not in _encoders:
-        _encoders[key] = H264Encoder(qp, device, gop, search, subpel)
+        _encoders[key] = H264Encoder(qp, device, gop, search, subpel, intra4)
     return _encoders[key]

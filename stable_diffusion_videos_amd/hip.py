@@ -122,6 +122,11 @@ _H264_SUB_SIGNATURES = {
     "sdv_h264_encode_gop_step_sub": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
 }
 H264_SUB_SYMBOLS = tuple(_H264_SUB_SIGNATURES)
+# include/sdv_hip_h264_i4.h: the IDR pictures of a call with Intra4x4 prediction (the arguments of sdv_h264_encode_gops)
+_H264_I4_SIGNATURES = {
+    "sdv_h264_encode_idr4": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+}
+H264_I4_SYMBOLS = tuple(_H264_I4_SIGNATURES)
 
 
 def lib_path() -> Path:
@@ -142,7 +147,7 @@ def load(build_if_missing: bool = False):
                 f"{_LIB_PATH} is missing - build it with `python -m stable_diffusion_videos_amd.build` "
                 "(there is no CPU / eager fallback for the hot path)")
     lib = C.CDLL(str(_LIB_PATH))
-    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES, **_H264_I4_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1775,6 +1780,44 @@ def h264_encode_gop_step_sub(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor
     prediction (rule of sdv_hip_h264_sub.h; ``torch.ops.sdv.k_h264_encode_gop_step_sub`` -> sdv_h264_encode_gop_step_sub).  Call it for
     k = 0 .. min(gop, n) - 1 in order on one stream."""
     _k_h264_encode_gop_step_sub(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch)
+
+
+def _h264_encode_idr4_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch):
+    what = "h264_encode_idr4"
+    n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    if mbw > H264_GOP_MAX_MBW:
+        raise SdvHipError(f"{what}: pictures wider than {H264_GOP_MAX_MBW} macroblocks are not coded in the GOP path's slots, got mbw={mbw}")
+    if first_index < 0:
+        raise SdvHipError(f"{what}: first_index must be >= 0, got {first_index}")
+    _h264_u8(what, "ry", ry, y.shape)
+    _h264_u8(what, "rcb", rcb, cb.shape)
+    _h264_u8(what, "rcr", rcr, cr.shape)
+    _h264_u8(what, "scratch", scratch)
+    need = h264_gop_scratch_bytes(n, mbh, mbw)
+    if scratch.ndim != 1 or scratch.numel() < need:
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n * mbh} slices of {mbw} macroblocks need {need}")
+    lib = load()
+    args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(first_index) & 0x7fffffff,
+            _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"), _ptr(scratch, name="scratch"), scratch.numel())
+    _launch("h264_encode_idr4", dict(bytes=3.0 * y.numel() / gop), lambda: _check(lib.sdv_h264_encode_idr4(*args, _stream()), "sdv_h264_encode_idr4"))
+
+
+_k_h264_encode_idr4 = _defop("k_h264_encode_idr4(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int first_index, Tensor(a!) ry, Tensor(b!) rcb, "
+                             "Tensor(c!) rcr, Tensor(d!) scratch) -> ()", _h264_encode_idr4_impl)
+
+
+def h264_encode_idr4(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, first_index: int, ry: torch.Tensor,
+                     rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor):
+    """Code the IDR pictures of a call (positions ``k % gop == 0``; every picture at ``gop`` 1) with Intra4x4 prediction: per macroblock
+    ``I_NxN`` against Intra16x16 DC by the stream rule of sdv_hip_h264_i4.h (``torch.ops.sdv.k_h264_encode_idr4`` ->
+    sdv_h264_encode_idr4).  Slices go to the GOP slots of ``scratch`` (``h264_gop_scratch_bytes``; pack with ``h264_gop_slot_mbw(mbw)``), all
+    their reconstructed samples to ``ry`` / ``rcb`` / ``rcr``; the P pictures follow through ``h264_encode_gop_step`` / ``_sub`` for
+    k = 1 .. min(gop, n) - 1."""
+    _k_h264_encode_idr4(y, cb, cr, int(qp), int(gop), int(first_index), ry, rcb, rcr, scratch)
 
 
 def _h264_pack_impl(scratch, n, mbh, mbw, out, offsets):

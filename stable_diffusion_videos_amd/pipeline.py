@@ -124,6 +124,7 @@ class StableDiffusionWalkPipeline:
         self.h264_gop = 1                  # pictures per IDR picture of the "h264-cavlc" track (1 .. 256; 1 = all intra); SDV_H264_GOP wins
         self.h264_search = 0               # motion search range of its P pictures in luma samples (even, 0 .. 16; 0 = none); SDV_H264_SEARCH wins
         self.h264_subpel = 0               # grid of those vectors: 0 = even whole samples, 1 = whole, 2 = half, 4 = quarter samples; SDV_H264_SUBPEL wins
+        self.h264_intra4 = 0               # 1 = its IDR pictures use Intra4x4 prediction (I_NxN against Intra16x16 per macroblock); SDV_H264_INTRA4 wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
         self.use_graphs = os.environ.get("SDV_NO_GRAPH", "0") != "1"
@@ -705,6 +706,20 @@ class StableDiffusionWalkPipeline:
             raise ValueError(f"SDV_H264_SUBPEL / h264_subpel must be 0, 1, 2 or 4, got {subpel!r}")
         return subpel
 
+    def h264_intra4_choice(self) -> int:
+        """Whether the IDR pictures of the ``h264-cavlc`` video track use Intra4x4 prediction: the environment variable SDV_H264_INTRA4
+        (0 or 1) when it is set, else ``self.h264_intra4``.  0 = every macroblock Intra16x16 DC; a setting, not a measured optimum."""
+        env = os.environ.get("SDV_H264_INTRA4")
+        if env is None or env == "":
+            intra4 = self.h264_intra4
+        elif env.isdigit():
+            intra4 = int(env)
+        else:
+            raise ValueError(f"SDV_H264_INTRA4 must be 0 or 1, got {env!r}")
+        if isinstance(intra4, bool) or not isinstance(intra4, int) or intra4 not in (0, 1):
+            raise ValueError(f"SDV_H264_INTRA4 / h264_intra4 must be 0 or 1, got {intra4!r}")
+        return intra4
+
     def make_clip_frames(self, prompt_a: str, prompt_b: str, seed_a: int, seed_b: int, num_interpolation_steps: int = 5,
                          save_path: Union[str, Path] = "outputs/", num_inference_steps: int = 50,
                          guidance_scale: float = 7.5, eta: float = 0.0, height: Optional[int] = None,
@@ -937,13 +952,15 @@ class StableDiffusionWalkPipeline:
                                 glob_pattern=f"*{image_file_ext}", audio_offset=audio_offset,
                                 audio_duration=num_step / fps, sr=44100, codec=self.video_codec,
                                 h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice(),
-                                h264_search=self.h264_search_choice(), h264_subpel=self.h264_subpel_choice())  # :787-796
+                                h264_search=self.h264_search_choice(), h264_subpel=self.h264_subpel_choice(),
+                                h264_intra4=self.h264_intra4_choice())                       # :787-796
             result = make_video_pyav(save_path_root, audio_filepath=audio_filepath, fps=fps, audio_offset=audio_start_sec,
                                      audio_duration=sum(num_interpolation_steps) / fps, output_filepath=output_filepath,
                                      glob_pattern=f"**/*{image_file_ext}", sr=44100, codec=self.video_codec,
                                      h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice(),
                                      h264_search=self.h264_search_choice(),
-                                     h264_subpel=self.h264_subpel_choice())                  # :798-807
+                                     h264_subpel=self.h264_subpel_choice(),
+                                     h264_intra4=self.h264_intra4_choice())                  # :798-807
         if world_size > 1:
             parallel.barrier()
             result = str(output_filepath) if result is None else result

@@ -1,6 +1,7 @@
 """GPU H.264 CAVLC intra encoder (h264_cavlc.H264Encoder) against the two video tracks it can stand in for, on the same box.
 
     python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N [--search R[,R...] [--subpel S[,S...]]]]
+    python tools/h264_bench.py [--out FILE] [--reps 5] --gop N[,N...] --search R[,R...] --intra4 0,1
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -27,6 +28,12 @@ With ``--gop N --search R --subpel S[,S...]`` (one R > 0; each S one of 0, 1, 2,
 search, the comparison of the same run: the columns above, the search kernel alone (sdv_h264_motion_search for S = 0,
 sdv_h264_motion_search_sub otherwise) and the share of vectors with a fractional component.  Frame sets as with ``--search`` plus
 ``glide``, the analytic texture of tests/h264_sub_ref.py that moves by a quarter sample a picture.
+With ``--intra4 I[,I...]`` (each I 0 or 1; ``--gop`` and ``--search`` may then be lists, a search > 0 is measured only at a gop > 1) the
+tool measures Intra4x4 prediction in the IDR pictures (h264_cavlc.H264Encoder(gop=N, search=R, intra4=I)): per frame set one row per
+(N, R, I) - I = 0 is the comparison of the same run: encode() ms and frames/s, bytes per frame, Y-PSNR of the reconstruction of all
+frames, the sdv_h264_encode_idr4 launch alone, and for I = 1 (512 x 512 sets, at the first N) the share of I_NxN macroblocks and the mode
+histogram of picture 0, read from its bytes by tests/h264_i4_ref.py's decoder.  Frame sets: the tiny pipeline's frames (128 x 512 x 512,
+and 8 x 2048 x 2048 through the x4 upsampler) and 48 x 512 x 512 frames of every kind of tests/h264_i4_ref.py.
 There is no fallback: without a GPU this tool fails.
 """
 from __future__ import annotations
@@ -224,6 +231,79 @@ def measure_subpel(name: str, dev_frames: torch.Tensor, gop: int, search: int, s
     return rows
 
 
+def measure_intra4(name: str, frames, gops, searches, intra4s, reps: int) -> list:
+    """``frames``: uint8 NHWC frames in GPU memory, or padded planes (y, cb, cr) for the kinds that exist as planes only."""
+    import h264_i4_ref as I4
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    planes = isinstance(frames, tuple)
+    y, cb, cr = frames if planes else hip.h264_planes(frames)
+    n, H, W = y.shape if planes else frames.shape[:3]
+    mbh, mbw = y.shape[1] // 16, y.shape[2] // 16
+    rows = []
+    for gop in gops:
+        for search in searches:
+            if search and gop == 1:
+                continue
+            for intra4 in intra4s:
+                enc = H264Encoder(16, y.device, gop=gop, search=search, intra4=intra4)
+                run = (lambda **kw: enc.encode_planes(y, cb, cr, **kw)) if planes else (lambda **kw: enc.encode(frames, **kw))
+                ev, wall = timed(run, reps)
+                if intra4 or gop > 1:
+                    samples, recon = run(return_recon=True)
+                    mse = float(((recon[0][:, :H, :W].to(torch.float64) - y[:, :H, :W].to(torch.float64)) ** 2).mean())
+                    psnr = round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None
+                else:                                                               # the all-intra rows kernel keeps no reconstruction
+                    samples, psnr = run(), None
+                row = dict(content=name, n=n, H=H, W=W, qp=16, gop=gop, search=search, intra4=intra4, encode_ms_events=round(ev, 3),
+                           encode_ms_host_clock=round(wall, 3), frames_per_sec=round(n / wall * 1e3, 1),
+                           bytes_per_frame=int(sum(len(s) for s in samples) // n), y_psnr_db=psnr)
+                if intra4:
+                    recon = [torch.empty_like(p) for p in (y, cb, cr)]
+                    scratch = torch.empty((hip.h264_gop_scratch_bytes(n, mbh, mbw),), dtype=torch.uint8, device=y.device)
+                    ms = timed(lambda: hip.h264_encode_idr4(y, cb, cr, 16, gop, 0, *recon, scratch), reps)[0]
+                    row.update(idr4_kernel_ms=round(ms, 3), idr4_share_of_encode=round(ms / ev, 3))
+                    del recon, scratch
+                    if H * W <= 512 * 512 and gop == gops[0] and not search:
+                        d = I4.decode_stream(samples[:1], W, H)
+                        row.update(i_nxn_share_picture0=round(d["n_i4"] / (mbh * mbw), 4), pcm_share_picture0=round(d["n_pcm"] / (mbh * mbw), 4),
+                                   mode_histogram_picture0=d["i4_modes"])
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+                del enc
+                torch.cuda.empty_cache()
+    return rows
+
+
+def main_intra4(args):
+    import h264_i4_ref as I4
+    from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
+    from stable_diffusion_videos_amd.upsampling import RealESRGANModel
+    dev = torch.device("cuda", 0)
+    result = dict(tool=f"tools/h264_bench.py --gop {args.gop} --search {args.search} --intra4 {args.intra4}", gpu=torch.cuda.get_device_name(0),
+                  host=platform.processor() or platform.machine(), reps=args.reps, qp=16, rows=[])
+    pipe = StableDiffusionWalkPipeline.from_pretrained("tiny").to(dev)
+    small = pipeline_frames(pipe, 128)
+    up = RealESRGANModel.from_pretrained("nateraw/real-esrgan")
+    up.to(dev)
+    big = torch.cat([up.upsample_u8(small[k:k + 2]) for k in range(0, 8, 2)])
+    del pipe, up
+    sets = [("tiny pipeline", lambda: small.contiguous()), ("tiny pipeline x4 upsampler", lambda: big.contiguous())]
+    for kind in I4.KINDS:
+        if kind.endswith("_pcm"):
+            sets.append((kind, lambda kind=kind: tuple(torch.from_numpy(p).to(dev) for p in I4.make_planes(kind, 48, 512, 512))))
+        else:
+            sets.append((kind, lambda kind=kind: torch.from_numpy(I4.make_frames(kind, 48, 512, 512)).to(dev).contiguous()))
+    for name, make in sets:
+        result["rows"] += measure_intra4(name, make(), args.gops, args.searches, args.intra4s, args.reps)
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    print(line)
+
+
 def main_gop(args):
     from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
     from stable_diffusion_videos_amd.upsampling import RealESRGANModel
@@ -266,10 +346,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--gop", type=int, default=1, help="N > 1: measure the GOP path, rows for gop 1 and gop N side by side")
+    ap.add_argument("--gop", default="1", help="N > 1: measure the GOP path, rows for gop 1 and gop N side by side (with --intra4: N[,N...])")
     ap.add_argument("--search", default=None, help="with --gop N: R[,R...] (even, 0 .. 16): one row per motion search range, 0 = none")
     ap.add_argument("--subpel", default=None, help="with --gop N --search R (one R > 0): S[,S...] (0, 1, 2, 4): one row per vector grid, 0 = even samples")
+    ap.add_argument("--intra4", default=None, help="I[,I...] (0, 1): one row per (gop, search, I); --gop and --search are then lists, 0 = Intra16x16 only")
     args = ap.parse_args()
+    if args.intra4 is not None:
+        args.gops = [int(v) for v in args.gop.split(",")]
+        args.searches = [int(v) for v in (args.search or "0").split(",")]
+        args.search = args.search or "0"
+        args.intra4s = [int(v) for v in args.intra4.split(",")]
+        if args.subpel is not None or any(not 1 <= v <= 256 for v in args.gops) or any(v % 2 or not 0 <= v <= 16 for v in args.searches) \
+                or any(v not in (0, 1) for v in args.intra4s):
+            raise SystemExit("--intra4 takes 0 and 1, with --gop N[,N...] (1 .. 256) and --search R[,R...] (even, 0 .. 16), without --subpel")
+        if not torch.cuda.is_available():
+            raise SystemExit("h264_bench needs the GPU (no fallback)")
+        return main_intra4(args)
+    args.gop = int(args.gop)
     if args.search is not None:
         if args.gop == 1:
             raise SystemExit("--search needs --gop N > 1 (there are no P pictures at gop 1)")
