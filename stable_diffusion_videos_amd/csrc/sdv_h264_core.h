@@ -394,7 +394,7 @@ H264_HD int h264_encode_mb(const uint8_t* sy, const uint8_t* sc, int16_t* lev, h
 }
 
 template <class Sink>
-H264_HD void h264_slice_header(Sink& s, unsigned first_mb, unsigned idr_pic_id, int qp) {
+H264_HD void h264_slice_header(Sink& s, unsigned first_mb, unsigned idr_pic_id, int qp, int deblock = 0) {
     h264_put_ue(s, first_mb);
     h264_put_ue(s, 7u);                                 // slice_type: I, and every slice of the picture is
     h264_put_ue(s, 0u);                                 // pic_parameter_set_id
@@ -402,7 +402,12 @@ H264_HD void h264_slice_header(Sink& s, unsigned first_mb, unsigned idr_pic_id, 
     h264_put_ue(s, idr_pic_id);
     s.put(0u, 2);                                       // no_output_of_prior_pics_flag, long_term_reference_flag
     h264_put_se(s, qp - 26);                            // slice_qp_delta against pic_init_qp 26
-    h264_put_ue(s, 1u);                                 // disable_deblocking_filter_idc
+    if (deblock) {                                      // "H.264 deblocking" (sdv_hip_h264_lf.h): the same three bits
+        h264_put_ue(s, 0u);                             // disable_deblocking_filter_idc
+        h264_put_se(s, 0), h264_put_se(s, 0);           // slice_alpha_c0_offset_div2, slice_beta_offset_div2
+    } else {
+        h264_put_ue(s, 1u);                             // disable_deblocking_filter_idc
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -680,7 +685,7 @@ H264_HD void h264_gop_chain(const h264_gop_mb* mb, h264_chain& ch) {
 
 // P slice header (7.3.3): frame_num u(4), no override, no list modification, sliding-window marking
 template <class Sink>
-H264_HD void h264_p_slice_header(Sink& s, unsigned first_mb, unsigned frame_num, int qp) {
+H264_HD void h264_p_slice_header(Sink& s, unsigned first_mb, unsigned frame_num, int qp, int deblock = 0) {
     h264_put_ue(s, first_mb);
     h264_put_ue(s, 5u);                                 // slice_type: P, and every slice of the picture is
     h264_put_ue(s, 0u);                                 // pic_parameter_set_id
@@ -688,7 +693,12 @@ H264_HD void h264_p_slice_header(Sink& s, unsigned first_mb, unsigned frame_num,
     s.put(0u, 3);                                       // num_ref_idx_active_override_flag, ref_pic_list_modification_flag_l0,
                                                         // adaptive_ref_pic_marking_mode_flag
     h264_put_se(s, qp - 26);
-    h264_put_ue(s, 1u);                                 // disable_deblocking_filter_idc
+    if (deblock) {                                      // "H.264 deblocking" (sdv_hip_h264_lf.h): the same three bits
+        h264_put_ue(s, 0u);                             // disable_deblocking_filter_idc
+        h264_put_se(s, 0), h264_put_se(s, 0);           // slice_alpha_c0_offset_div2, slice_beta_offset_div2
+    } else {
+        h264_put_ue(s, 1u);                             // disable_deblocking_filter_idc
+    }
 }
 
 // The whole macroblock step in order, one piece after the other (host; the kernel spreads the per-block pieces over its lanes).
@@ -1341,4 +1351,179 @@ inline int h264_i4_encode_mb(h264_gop_mb* mb, h264_i4_mb* s, h264_i4_chain& ch, 
     for (int b = 0; b < 24; ++b) h264_i4_block_recon(mb, b, qp);
     h264_gop_chain(mb, ch.ch);
     return mb->mode;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// In-loop deblocking filter (sdv_hip_h264_lf.h "H.264 deblocking"): 8.7 for frame macroblocks, 4:2:0, no 8x8 transform, filterOffsetA =
+// filterOffsetB = 0, one reference picture.  The pieces below are per line of one edge: the side information word of a macroblock, bS,
+// the index into the tables, and the one sample filter.  The kernel gives a line to a lane (an LDS window of the macroblock and its
+// neighbours); h264_lf_picture walks the macroblocks in raster order on the planes themselves.  Above, only the two slice header
+// functions changed: a defaulted argument ``deblock`` that switches the filter on in the header.
+// ------------------------------------------------------------------------------------------------------------------------------------
+// mbinfo word of a macroblock: bits 0 .. 15 bit 4 by + bx set when luma block (bx, by) of an INTER macroblock kept a nonzero level (0 in
+// every other macroblock); bit 16 intra (Intra16x16, I_NxN, I_PCM); bit 17 I_PCM; bit 18 the coded vector is (0, 0) whatever ``mv``
+// holds (P_Skip, or a vector the stream rule did not admit); bits 19 .. 31 zero.
+enum { kH264LfIntra = 1 << 16, kH264LfPcm = 1 << 17, kH264LfZeroMv = 1 << 18 };
+
+H264_HD unsigned h264_lf_nz_raster(unsigned nz) {       // bit luma4x4BlkIdx -> bit 4 by + bx
+    unsigned r = 0;
+    for (int b = 0; b < 16; ++b) {
+        int x, y;
+        h264_gop_block_xy(b, &x, &y);
+        if ((nz >> b) & 1u) r |= 1u << (y + (x >> 2));
+    }
+    return r;
+}
+// mode: h264_gop_mb::mode after the serial piece; nz: the ballot of h264_gop_block_forward; (vx, vy): the vector that was coded
+H264_HD uint32_t h264_lf_word(int mode, unsigned nz, int vx, int vy) {
+    if (mode == kH264ModePcm) return (uint32_t)(kH264LfIntra | kH264LfPcm);
+    if (mode == kH264ModeIntra || mode == kH264ModeI4) return (uint32_t)kH264LfIntra;
+    return (mode == kH264ModeInter ? h264_lf_nz_raster(nz & 0xffffu) : 0u) | (!vx && !vy ? (uint32_t)kH264LfZeroMv : 0u);
+}
+
+H264_HD int h264_lf_alpha(int index) {                  // Table 8-16, alpha'
+    const uint8_t t[52] = {0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  4,  4,  5,  6,  7,  8,   9,   10,  12,  13,
+                           15, 17, 20, 22, 25, 28, 32, 36, 40, 45, 50, 56, 63, 71, 80, 90, 101, 113, 127, 144, 162, 182, 203, 226, 255, 255};
+    return t[index];
+}
+H264_HD int h264_lf_beta(int index) {                   // Table 8-16, beta'
+    const uint8_t t[52] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,  0,  0,  0,  0,  0,  2,  2,  2,  3,  3,  3,  3,  4,  4,  4,
+                           6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13, 14, 14, 15, 15, 16, 16, 17, 17, 18, 18};
+    return t[index];
+}
+H264_HD int h264_lf_tc0(int index, int bS) {            // Table 8-17, tC0' for bS 1, 2, 3
+    const uint8_t t[3][52] = {
+        {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6, 6, 7, 8, 9, 10, 11, 13},
+        {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5, 5, 6, 7, 8, 8, 10, 11, 12, 13, 15, 17},
+        {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6, 6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 23, 25}};
+    return t[bS - 1][index];
+}
+
+// One side of an edge: the macroblock's word and its vector in QUARTER samples ((0, 0) for an intra macroblock and under bit 18).
+// ``mv`` holds even whole samples without subpel and quarter samples with it.
+struct h264_lf_side {
+    uint32_t info;
+    int vx, vy;
+};
+H264_HD h264_lf_side h264_lf_side_of(uint32_t info, const int16_t* v, int subpel) {
+    h264_lf_side s;
+    const bool zero = (info & (uint32_t)(kH264LfIntra | kH264LfZeroMv)) != 0;
+    const int scale = subpel ? 1 : 4;
+    s.info = info;
+    s.vx = zero ? 0 : (int)v[0] * scale, s.vy = zero ? 0 : (int)v[1] * scale;
+    return s;
+}
+// bS of the edge between luma block pblk of P and qblk of Q (4 by + bx each); mb_edge: the two lie in different macroblocks
+H264_HD int h264_lf_bs(const h264_lf_side& p, int pblk, const h264_lf_side& q, int qblk, bool mb_edge) {
+    if ((p.info | q.info) & (uint32_t)kH264LfIntra) return mb_edge ? 4 : 3;
+    if (((p.info >> pblk) | (q.info >> qblk)) & 1u) return 2;
+    const int dx = p.vx - q.vx, dy = p.vy - q.vy;
+    return (dx >= 4 || dx <= -4 || dy >= 4 || dy <= -4) ? 1 : 0;
+}
+// indexA = indexB of an edge: qPp / qPq are 0 for I_PCM and the slice qp otherwise, each through Table 8-15 first for chroma
+H264_HD int h264_lf_index(const h264_lf_side& p, const h264_lf_side& q, int qp, bool chroma) {
+    int a = (p.info & (uint32_t)kH264LfPcm) ? 0 : qp, b = (q.info & (uint32_t)kH264LfPcm) ? 0 : qp;
+    if (chroma) a = h264_qpc(a), b = h264_qpc(b);
+    const int i = (a + b + 1) >> 1;
+    return i < 0 ? 0 : i > 51 ? 51 : i;
+}
+// 8.7.2.3 / 8.7.2.4 for one line: q0 at ``q``, q_i at q[i * step], p_i at q[-(i + 1) * step].  bS 1 .. 4.
+H264_HD void h264_lf_line(uint8_t* q, int step, int bS, int index, bool chroma) {
+    const int alpha = h264_lf_alpha(index), beta = h264_lf_beta(index);
+    const int p0 = q[-step], p1 = q[-2 * step], q0 = q[0], q1 = q[step];
+    const int d0 = p0 - q0, dp = p1 - p0, dq = q1 - q0;
+    if (!((d0 < 0 ? -d0 : d0) < alpha && (dp < 0 ? -dp : dp) < beta && (dq < 0 ? -dq : dq) < beta)) return;
+    if (chroma) {
+        if (bS < 4) {
+            const int tc = h264_lf_tc0(index, bS) + 1;
+            int delta = (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3;
+            delta = delta < -tc ? -tc : delta > tc ? tc : delta;
+            q[-step] = (uint8_t)h264_clip255(p0 + delta), q[0] = (uint8_t)h264_clip255(q0 - delta);
+        } else {
+            q[-step] = (uint8_t)((2 * p1 + p0 + q1 + 2) >> 2), q[0] = (uint8_t)((2 * q1 + q0 + p1 + 2) >> 2);
+        }
+        return;
+    }
+    const int p2 = q[-3 * step], q2 = q[2 * step];
+    const int ap = p2 - p0 < 0 ? p0 - p2 : p2 - p0, aq = q2 - q0 < 0 ? q0 - q2 : q2 - q0;
+    if (bS < 4) {
+        const int tc0 = h264_lf_tc0(index, bS), tc = tc0 + (ap < beta ? 1 : 0) + (aq < beta ? 1 : 0);
+        int delta = (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3;
+        delta = delta < -tc ? -tc : delta > tc ? tc : delta;
+        q[-step] = (uint8_t)h264_clip255(p0 + delta), q[0] = (uint8_t)h264_clip255(q0 - delta);
+        if (ap < beta) {
+            int d = (p2 + ((p0 + q0 + 1) >> 1) - 2 * p1) >> 1;
+            d = d < -tc0 ? -tc0 : d > tc0 ? tc0 : d;
+            q[-2 * step] = (uint8_t)(p1 + d);
+        }
+        if (aq < beta) {
+            int d = (q2 + ((p0 + q0 + 1) >> 1) - 2 * q1) >> 1;
+            d = d < -tc0 ? -tc0 : d > tc0 ? tc0 : d;
+            q[step] = (uint8_t)(q1 + d);
+        }
+        return;
+    }
+    const bool small = (d0 < 0 ? -d0 : d0) < (alpha >> 2) + 2;
+    if (ap < beta && small) {
+        const int p3 = q[-4 * step];
+        q[-step] = (uint8_t)((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3);
+        q[-2 * step] = (uint8_t)((p2 + p1 + p0 + q0 + 2) >> 2);
+        q[-3 * step] = (uint8_t)((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3);
+    } else {
+        q[-step] = (uint8_t)((2 * p1 + p0 + q1 + 2) >> 2);
+    }
+    if (aq < beta && small) {
+        const int q3 = q[3 * step];
+        q[0] = (uint8_t)((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3);
+        q[step] = (uint8_t)((p0 + q0 + q1 + q2 + 2) >> 2);
+        q[2 * step] = (uint8_t)((2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3);
+    } else {
+        q[0] = (uint8_t)((2 * q1 + q0 + p1 + 2) >> 2);
+    }
+}
+// Line l (0 .. 15) of luma edge e (0 .. 3) of macroblock Q, whose sample (0, 0) is mb[0] in rows of ``stride``: dir 0 the vertical edge
+// at column 4 e (l a row), dir 1 the horizontal edge at row 4 e (l a column).  p: the left / upper neighbour for e = 0, Q itself else.
+H264_HD void h264_lf_luma_line(uint8_t* mb, int stride, int dir, int e, int l, const h264_lf_side& p, const h264_lf_side& q, int qp) {
+    const int along = l >> 2, pe = e ? e - 1 : 3;
+    const int qblk = dir ? 4 * e + along : 4 * along + e, pblk = dir ? 4 * pe + along : 4 * along + pe;
+    const int bS = h264_lf_bs(p, pblk, q, qblk, e == 0);
+    if (!bS) return;
+    h264_lf_line(dir ? mb + 4 * e * stride + l : mb + l * stride + 4 * e, dir ? stride : 1, bS, h264_lf_index(p, q, qp, false), false);
+}
+// Line l (0 .. 7) of chroma edge c (0, 1: chroma column / row 4 c) of one chroma plane of macroblock Q: its bS is that of luma edge 2 c at
+// the luma lines 2 l and 2 l + 1, which lie in one 4x4 block.
+H264_HD void h264_lf_chroma_line(uint8_t* mb, int stride, int dir, int c, int l, const h264_lf_side& p, const h264_lf_side& q, int qp) {
+    const int e = 2 * c, along = l >> 1, pe = e ? e - 1 : 3;
+    const int qblk = dir ? 4 * e + along : 4 * along + e, pblk = dir ? 4 * pe + along : 4 * along + pe;
+    const int bS = h264_lf_bs(p, pblk, q, qblk, e == 0);
+    if (!bS) return;
+    h264_lf_line(dir ? mb + 4 * c * stride + l : mb + l * stride + 4 * c, dir ? stride : 1, bS, h264_lf_index(p, q, qp, true), true);
+}
+
+// The whole filter of one picture in the standard's order, on the planes themselves (host): macroblocks in raster order; in each luma
+// vertical edges left to right, luma horizontal edges top to bottom, then the same for Cb and for Cr.  The left and top picture edges are
+// not filtered.  info [mbh * mbw], mv [mbh * mbw * 2].
+inline void h264_lf_picture(uint8_t* ry, uint8_t* rcb, uint8_t* rcr, int mbh, int mbw, int qp, const uint32_t* info, const int16_t* mv, int subpel) {
+    const int lw = 16 * mbw, cw = 8 * mbw;
+    for (int my = 0; my < mbh; ++my)
+        for (int mx = 0; mx < mbw; ++mx) {
+            const int at = my * mbw + mx;
+            const h264_lf_side q = h264_lf_side_of(info[at], mv + 2 * at, subpel);
+            const h264_lf_side left = mx ? h264_lf_side_of(info[at - 1], mv + 2 * (at - 1), subpel) : q;
+            const h264_lf_side up = my ? h264_lf_side_of(info[at - mbw], mv + 2 * (at - mbw), subpel) : q;
+            uint8_t* y0 = ry + (long long)my * 16 * lw + mx * 16;
+            for (int dir = 0; dir < 2; ++dir)
+                for (int e = 0; e < 4; ++e) {
+                    if (e == 0 && !(dir ? my : mx)) continue;
+                    for (int l = 0; l < 16; ++l) h264_lf_luma_line(y0, lw, dir, e, l, e ? q : dir ? up : left, q, qp);
+                }
+            for (int c = 0; c < 2; ++c) {
+                uint8_t* c0 = (c ? rcr : rcb) + (long long)my * 8 * cw + mx * 8;
+                for (int dir = 0; dir < 2; ++dir)
+                    for (int e = 0; e < 2; ++e) {
+                        if (e == 0 && !(dir ? my : mx)) continue;
+                        for (int l = 0; l < 8; ++l) h264_lf_chroma_line(c0, cw, dir, e, l, e ? q : dir ? up : left, q, qp);
+                    }
+            }
+        }
 }

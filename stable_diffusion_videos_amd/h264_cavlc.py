@@ -25,6 +25,12 @@ kernel of its own that chooses per macroblock between ``I_NxN`` (Intra4x4 predic
 macroblock above; P pictures are untouched.  tests/h264_i4_ref.py restates and decodes it.  ``intra4`` 0 is the code and the bytes of
 the other settings alone.
 
+``deblock`` 1 (opt-in, with every other setting; include/sdv_hip_h264_lf.h and DESIGN.md "H.264 deblocking") switches the in-loop
+deblocking filter on: the slice headers say so, every picture position goes through a per-position entry point that also leaves one side
+information word per macroblock, and a filter launch between two positions rewrites the reconstruction planes in place, so P pictures
+predict from filtered pictures.  tests/h264_lf_ref.py restates, decodes and filters it.  ``deblock`` 0 is the code and the bytes of the
+other settings alone.
+
 Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
 """
 from __future__ import annotations
@@ -40,6 +46,7 @@ DEFAULT_GOP = 1                                                                 
 DEFAULT_SEARCH = 0                                                                              # a setting, not a measured optimum
 DEFAULT_SUBPEL = 0                                                                              # a setting, not a measured optimum
 DEFAULT_INTRA4 = 0                                                                              # a setting, not a measured optimum
+DEFAULT_DEBLOCK = 0                                                                             # a setting, not a measured optimum
 
 
 def check_qp(qp) -> int:
@@ -72,6 +79,12 @@ def check_intra4(intra4) -> int:
     return intra4
 
 
+def check_deblock(deblock) -> int:
+    if isinstance(deblock, bool) or not isinstance(deblock, int) or deblock not in (0, 1):
+        raise ValueError(f"h264 deblock must be one of the integers 0, 1, got {deblock!r}")
+    return deblock
+
+
 class H264Encoder:
     """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
     (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.  With ``gop``
@@ -83,19 +96,22 @@ class H264Encoder:
     effect unless ``gop`` > 1 and ``search`` > 0) runs the same number of launches through the quarter-sample pair of entry points.
     ``intra4`` 1 codes the IDR pictures with Intra4x4 prediction: one launch for all of them, then one launch per P picture position
     (always the per-position entry points, with zero vectors when ``search`` is 0); the workspaces are then those of the GOP path at
-    any ``gop``, so ``return_recon`` works at ``gop`` 1 too.
+    any ``gop``, so ``return_recon`` works at ``gop`` 1 too.  ``deblock`` 1 switches the in-loop deblocking filter on: every picture
+    position through a per-position entry point (the IDR pictures through the k = 0 step, or the Intra4x4 launch), and one filter launch
+    after each position but the last, whose filtered planes only ``return_recon`` reads (it then runs too); GOP workspaces at any ``gop``.
 
     Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
     prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
     capacity bound of sdv_hip.h, so no batch can fail to fit."""
 
     def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH,
-                 subpel: int = DEFAULT_SUBPEL, intra4: int = DEFAULT_INTRA4):
+                 subpel: int = DEFAULT_SUBPEL, intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK):
         self.qp = check_qp(qp)
         self.gop = check_gop(gop)
         self.search = check_search(search)
         self.subpel = check_subpel(subpel)
         self.intra4 = check_intra4(intra4)
+        self.deblock = check_deblock(deblock)
         self.last_sync: List[int] = []
         self.device = torch.device(device) if device is not None else None
         self._ws: Dict[tuple, dict] = {}
@@ -105,7 +121,7 @@ class H264Encoder:
         key = (n, mbh, mbw, str(device))
         ws = self._ws.get(key)
         if ws is None:
-            gops = self.gop > 1 or self.intra4 == 1                                          # Intra4x4 uses the GOP slots at any gop
+            gops = self.gop > 1 or self.intra4 == 1 or self.deblock == 1                     # Intra4x4 and the loop filter use the GOP slots at any gop
             cap = hip.h264_gop_out_bytes(n, mbh, mbw) if gops else hip.h264_out_bytes(n, mbh, mbw)
             scratch = hip.h264_gop_scratch_bytes(n, mbh, mbw) if gops else hip.h264_scratch_bytes(n, mbh, mbw)
             ws = dict(y=torch.empty((n, 16 * mbh, 16 * mbw), dtype=torch.uint8, device=device),
@@ -118,7 +134,10 @@ class H264Encoder:
                       out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True))
             if gops:                                                                            # the reference pictures stay in HBM
                 ws.update(ry=torch.empty_like(ws["y"]), rcb=torch.empty_like(ws["cb"]), rcr=torch.empty_like(ws["cr"]))
-                if self.search and self.gop > 1:                                                # even samples, or quarter samples with subpel
+                if self.deblock:                                                                # the filter reads the vectors of every picture
+                    ws.update(mv=torch.zeros((n, mbh, mbw, 2), dtype=torch.int16, device=device),
+                              mbinfo=torch.zeros((n, mbh, mbw), dtype=torch.int32, device=device))
+                elif self.search and self.gop > 1:                                              # even samples, or quarter samples with subpel
                     ws.update(mv=torch.empty((n, mbh, mbw, 2), dtype=torch.int16, device=device))
                 elif self.intra4 and self.gop > 1:                                              # zero vectors for the per-position entry point
                     ws.update(mv=torch.zeros((n, mbh, mbw, 2), dtype=torch.int16, device=device))
@@ -163,7 +182,10 @@ class H264Encoder:
             return self._rows_and_pack(ws, n, mbh, mbw, first_index, return_recon)
 
     def _rows_and_pack(self, ws: dict, n: int, mbh: int, mbw: int, first_index: int, return_recon: bool = False):
-        if self.intra4:
+        if self.deblock:
+            self._deblocked_steps(ws, n, int(first_index), return_recon)
+            hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
+        elif self.intra4:
             self._idr4_and_steps(ws, n, int(first_index))
             hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
         elif self.gop == 1:
@@ -217,13 +239,39 @@ class H264Encoder:
                 hip.h264_encode_gop_step(*planes, self.qp, self.gop, k, self.search or 2, first_index, ws["mv"], *recon, ws["scratch"])
 
 
+    def _deblocked_steps(self, ws: dict, n: int, first_index: int, filter_last: bool):
+        """``deblock``: every picture position through its per-position entry point with the side information, the filter between two
+        positions.  IDR pictures take the Intra4x4 launch with ``intra4`` and the k = 0 step without; without a search the P pictures
+        take the whole-sample entry point with its smallest range and zero vectors."""
+        planes, recon = (ws["y"], ws["cb"], ws["cr"]), (ws["ry"], ws["rcb"], ws["rcr"])
+        last = min(self.gop, n)
+        searched = bool(self.search) and self.gop > 1
+        sub = self.subpel if searched else 0
+        if last > 1 and sub:
+            hip.h264_motion_search_sub(ws["y"], self.qp, self.gop, self.search, sub, ws["mv"])
+        elif last > 1 and searched:
+            hip.h264_motion_search(ws["y"], self.qp, self.gop, self.search, ws["mv"])
+        for k in range(last):
+            if k == 0 and self.intra4:
+                hip.h264_encode_idr4_lf(*planes, self.qp, self.gop, first_index, *recon, ws["scratch"], ws["mbinfo"])
+            elif sub:
+                hip.h264_encode_gop_step_sub_lf(*planes, self.qp, self.gop, k, self.search, sub, first_index, ws["mv"], *recon, ws["scratch"],
+                                                ws["mbinfo"])
+            else:
+                hip.h264_encode_gop_step_lf(*planes, self.qp, self.gop, k, self.search if searched else 2, first_index, ws["mv"], *recon,
+                                            ws["scratch"], ws["mbinfo"])
+            if k + 1 < last or filter_last:
+                hip.h264_deblock(*recon, self.qp, self.gop, k, sub, ws["mbinfo"], ws["mv"])
+
+
 _encoders: Dict[tuple, H264Encoder] = {}
 
 
 def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH, subpel: int = DEFAULT_SUBPEL,
-                intra4: int = DEFAULT_INTRA4) -> H264Encoder:
-    """One cached encoder (and its workspaces) per quality setting, GOP length, search range, vector grid, intra setting and device."""
-    key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel), check_intra4(intra4))
+                intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK) -> H264Encoder:
+    """One cached encoder (and its workspaces) per quality setting, GOP length, search range, vector grid, intra setting, loop filter
+    setting and device."""
+    key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel), check_intra4(intra4), check_deblock(deblock))
     if key not in _encoders:
-        _encoders[key] = H264Encoder(qp, device, gop, search, subpel, intra4)
+        _encoders[key] = H264Encoder(qp, device, gop, search, subpel, intra4, deblock)
     return _encoders[key]

@@ -127,6 +127,14 @@ _H264_I4_SIGNATURES = {
     "sdv_h264_encode_idr4": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
 }
 H264_I4_SYMBOLS = tuple(_H264_I4_SIGNATURES)
+# include/sdv_hip_h264_lf.h: the in-loop deblocking filter, and the three per-position entry points with (mbinfo, mbinfo_count) before the stream
+_H264_LF_SIGNATURES = {
+    "sdv_h264_encode_gop_step_lf": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 8 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sdv_h264_encode_gop_step_sub_lf": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sdv_h264_encode_idr4_lf": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sdv_h264_deblock": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 7 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+}
+H264_LF_SYMBOLS = tuple(_H264_LF_SIGNATURES)
 
 
 def lib_path() -> Path:
@@ -147,7 +155,7 @@ def load(build_if_missing: bool = False):
                 f"{_LIB_PATH} is missing - build it with `python -m stable_diffusion_videos_amd.build` "
                 "(there is no CPU / eager fallback for the hot path)")
     lib = C.CDLL(str(_LIB_PATH))
-    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES, **_H264_I4_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES, **_H264_I4_SIGNATURES, **_H264_LF_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1649,9 +1657,23 @@ def h264_motion_search(y: torch.Tensor, qp: int, gop: int, search: int, mv: torc
     _k_h264_motion_search(y, int(qp), int(gop), int(search), mv, sad)
 
 
-def _h264_encode_gop_step_impl(y, cb, cr, qp, gop, k, search, first_index, mv, ry, rcb, rcr, scratch):
-    what = "h264_encode_gop_step"
+def _h264_mbinfo_check(what, mbinfo, n, mbh, mbw):
+    """The side information tensor of sdv_hip_h264_lf.h: int32 [n, mbh, mbw], contiguous."""
+    if not isinstance(mbinfo, torch.Tensor) or mbinfo.dtype != torch.int32 or not mbinfo.is_contiguous() or tuple(mbinfo.shape) != (n, mbh, mbw):
+        raise SdvHipError(f"{what}: mbinfo must be a contiguous int32 {[n, mbh, mbw]} tensor, got {getattr(mbinfo, 'dtype', type(mbinfo))} "
+                          f"{tuple(getattr(mbinfo, 'shape', ()))}")
+
+
+def _h264_mbinfo_args(what, mbinfo, n, mbh, mbw):
+    _h264_mbinfo_check(what, mbinfo, n, mbh, mbw)
+    return _ptr(mbinfo, name="mbinfo"), mbinfo.numel()
+
+
+def _h264_encode_gop_step_impl(y, cb, cr, qp, gop, k, search, first_index, mv, ry, rcb, rcr, scratch, mbinfo=None):
+    what = "h264_encode_gop_step" if mbinfo is None else "h264_encode_gop_step_lf"
     n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if mbinfo is not None:
+        _h264_mbinfo_check(what, mbinfo, n, mbh, mbw)
     if not 0 <= qp <= 51:
         raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
     if not 1 <= gop <= H264_GOP_MAX:
@@ -1677,6 +1699,11 @@ def _h264_encode_gop_step_impl(y, cb, cr, qp, gop, k, search, first_index, mv, r
     args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(k), int(search),
             int(first_index) & 0x7fffffff, _ptr(mv, name="mv"), _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"),
             _ptr(scratch, name="scratch"), scratch.numel())
+    if mbinfo is not None:
+        lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+        _launch("h264_encode_gop_step_lf", dict(bytes=3.0 * y.numel() / min(gop, n)),
+                lambda: _check(lib.sdv_h264_encode_gop_step_lf(*args, *lf, _stream()), "sdv_h264_encode_gop_step_lf"))
+        return
     _launch("h264_encode_gop_step", dict(bytes=3.0 * y.numel() / min(gop, n)),
             lambda: _check(lib.sdv_h264_encode_gop_step(*args, _stream()), "sdv_h264_encode_gop_step"))
 
@@ -1736,9 +1763,11 @@ def h264_motion_search_sub(y: torch.Tensor, qp: int, gop: int, search: int, subp
     _k_h264_motion_search_sub(y, int(qp), int(gop), int(search), int(subpel), mv, sad)
 
 
-def _h264_encode_gop_step_sub_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch):
-    what = "h264_encode_gop_step_sub"
+def _h264_encode_gop_step_sub_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch, mbinfo=None):
+    what = "h264_encode_gop_step_sub" if mbinfo is None else "h264_encode_gop_step_sub_lf"
     n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if mbinfo is not None:
+        _h264_mbinfo_check(what, mbinfo, n, mbh, mbw)
     if not 0 <= qp <= 51:
         raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
     if not 1 <= gop <= H264_GOP_MAX:
@@ -1765,6 +1794,11 @@ def _h264_encode_gop_step_sub_impl(y, cb, cr, qp, gop, k, search, subpel, first_
     args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(k), int(search), int(subpel),
             int(first_index) & 0x7fffffff, _ptr(mv, name="mv"), _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"),
             _ptr(scratch, name="scratch"), scratch.numel())
+    if mbinfo is not None:
+        lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+        _launch("h264_encode_gop_step_sub_lf", dict(bytes=3.0 * y.numel() / min(gop, n)),
+                lambda: _check(lib.sdv_h264_encode_gop_step_sub_lf(*args, *lf, _stream()), "sdv_h264_encode_gop_step_sub_lf"))
+        return
     _launch("h264_encode_gop_step_sub", dict(bytes=3.0 * y.numel() / min(gop, n)),
             lambda: _check(lib.sdv_h264_encode_gop_step_sub(*args, _stream()), "sdv_h264_encode_gop_step_sub"))
 
@@ -1782,9 +1816,11 @@ def h264_encode_gop_step_sub(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor
     _k_h264_encode_gop_step_sub(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch)
 
 
-def _h264_encode_idr4_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch):
-    what = "h264_encode_idr4"
+def _h264_encode_idr4_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, mbinfo=None):
+    what = "h264_encode_idr4" if mbinfo is None else "h264_encode_idr4_lf"
     n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if mbinfo is not None:
+        _h264_mbinfo_check(what, mbinfo, n, mbh, mbw)
     if not 0 <= qp <= 51:
         raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
     if not 1 <= gop <= H264_GOP_MAX:
@@ -1803,6 +1839,11 @@ def _h264_encode_idr4_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratc
     lib = load()
     args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(first_index) & 0x7fffffff,
             _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"), _ptr(scratch, name="scratch"), scratch.numel())
+    if mbinfo is not None:
+        lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+        _launch("h264_encode_idr4_lf", dict(bytes=3.0 * y.numel() / gop),
+                lambda: _check(lib.sdv_h264_encode_idr4_lf(*args, *lf, _stream()), "sdv_h264_encode_idr4_lf"))
+        return
     _launch("h264_encode_idr4", dict(bytes=3.0 * y.numel() / gop), lambda: _check(lib.sdv_h264_encode_idr4(*args, _stream()), "sdv_h264_encode_idr4"))
 
 
@@ -1818,6 +1859,97 @@ def h264_encode_idr4(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: in
     their reconstructed samples to ``ry`` / ``rcb`` / ``rcr``; the P pictures follow through ``h264_encode_gop_step`` / ``_sub`` for
     k = 1 .. min(gop, n) - 1."""
     _k_h264_encode_idr4(y, cb, cr, int(qp), int(gop), int(first_index), ry, rcb, rcr, scratch)
+
+
+def _h264_encode_gop_step_lf_impl(y, cb, cr, qp, gop, k, search, first_index, mv, ry, rcb, rcr, scratch, mbinfo):
+    _h264_encode_gop_step_impl(y, cb, cr, qp, gop, k, search, first_index, mv, ry, rcb, rcr, scratch, _h264_mbinfo_given("h264_encode_gop_step_lf", mbinfo))
+
+
+def _h264_encode_gop_step_sub_lf_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch, mbinfo):
+    _h264_encode_gop_step_sub_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch,
+                                   _h264_mbinfo_given("h264_encode_gop_step_sub_lf", mbinfo))
+
+
+def _h264_encode_idr4_lf_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, mbinfo):
+    _h264_encode_idr4_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, _h264_mbinfo_given("h264_encode_idr4_lf", mbinfo))
+
+
+def _h264_mbinfo_given(what, mbinfo):
+    if mbinfo is None:
+        raise SdvHipError(f"{what}: mbinfo is missing")
+    return mbinfo
+
+
+H264_LF_WAVES_MAX = 16
+
+
+def _h264_deblock_impl(ry, rcb, rcr, qp, gop, k, subpel, mbinfo, mv, waves):
+    what = "h264_deblock"
+    n, mbh, mbw = _h264_plane_grid(what, ry, rcb, rcr)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    if not 0 <= k < min(gop, n):
+        raise SdvHipError(f"{what}: position k must be 0 .. min(gop, n) - 1 = {min(gop, n) - 1}, got {k}")
+    if subpel not in (0,) + H264_SUBPELS:
+        raise SdvHipError(f"{what}: subpel must be 0, 1, 2 or 4, got {subpel}")
+    if not 0 <= waves <= H264_LF_WAVES_MAX:
+        raise SdvHipError(f"{what}: waves must be 0 (the default) .. {H264_LF_WAVES_MAX}, got {waves}")
+    if not isinstance(mv, torch.Tensor) or mv.dtype != torch.int16 or not mv.is_contiguous() or tuple(mv.shape) != (n, mbh, mbw, 2):
+        raise SdvHipError(f"{what}: mv must be a contiguous int16 {[n, mbh, mbw, 2]} tensor, got {getattr(mv, 'dtype', type(mv))} "
+                          f"{tuple(getattr(mv, 'shape', ()))}")
+    _h264_mbinfo_check(what, mbinfo, n, mbh, mbw)
+    lib = load()
+    lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+    args = (_ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"), n, mbh, mbw, int(qp), int(gop), int(k), int(subpel), *lf,
+            _ptr(mv, name="mv"), int(waves))
+    _launch("h264_deblock", dict(bytes=3.0 * ry.numel() / min(gop, n)), lambda: _check(lib.sdv_h264_deblock(*args, _stream()), "sdv_h264_deblock"))
+
+
+_k_h264_encode_gop_step_lf = _defop("k_h264_encode_gop_step_lf(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int k, int search, int first_index, "
+                                    "Tensor mv, Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch, Tensor(e!) mbinfo) -> ()",
+                                    _h264_encode_gop_step_lf_impl)
+_k_h264_encode_gop_step_sub_lf = _defop("k_h264_encode_gop_step_sub_lf(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int k, int search, int subpel, "
+                                        "int first_index, Tensor mv, Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch, "
+                                        "Tensor(e!) mbinfo) -> ()", _h264_encode_gop_step_sub_lf_impl)
+_k_h264_encode_idr4_lf = _defop("k_h264_encode_idr4_lf(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int first_index, Tensor(a!) ry, Tensor(b!) rcb, "
+                                "Tensor(c!) rcr, Tensor(d!) scratch, Tensor(e!) mbinfo) -> ()", _h264_encode_idr4_lf_impl)
+_k_h264_deblock = _defop("k_h264_deblock(Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, int qp, int gop, int k, int subpel, Tensor mbinfo, Tensor mv, "
+                         "int waves) -> ()", _h264_deblock_impl)
+
+
+def h264_encode_gop_step_lf(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, k: int, search: int, first_index: int,
+                            mv: torch.Tensor, ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor, mbinfo: torch.Tensor):
+    """``h264_encode_gop_step`` for a stream with the loop filter on (sdv_hip_h264_lf.h; ``torch.ops.sdv.k_h264_encode_gop_step_lf`` ->
+    sdv_h264_encode_gop_step_lf): the slice headers say so, and ``mbinfo`` (int32 ``[n, mbh, mbw]``) takes the side information word of
+    every macroblock coded.  ``h264_deblock`` for the same ``k`` follows before the next position."""
+    _k_h264_encode_gop_step_lf(y, cb, cr, int(qp), int(gop), int(k), int(search), int(first_index), mv, ry, rcb, rcr, scratch, mbinfo)
+
+
+def h264_encode_gop_step_sub_lf(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, k: int, search: int, subpel: int,
+                                first_index: int, mv: torch.Tensor, ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor,
+                                mbinfo: torch.Tensor):
+    """``h264_encode_gop_step_sub`` for a stream with the loop filter on (``torch.ops.sdv.k_h264_encode_gop_step_sub_lf`` ->
+    sdv_h264_encode_gop_step_sub_lf); see ``h264_encode_gop_step_lf``."""
+    _k_h264_encode_gop_step_sub_lf(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch,
+                                   mbinfo)
+
+
+def h264_encode_idr4_lf(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, first_index: int, ry: torch.Tensor,
+                        rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor, mbinfo: torch.Tensor):
+    """``h264_encode_idr4`` for a stream with the loop filter on (``torch.ops.sdv.k_h264_encode_idr4_lf`` -> sdv_h264_encode_idr4_lf); see
+    ``h264_encode_gop_step_lf``."""
+    _k_h264_encode_idr4_lf(y, cb, cr, int(qp), int(gop), int(first_index), ry, rcb, rcr, scratch, mbinfo)
+
+
+def h264_deblock(ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, qp: int, gop: int, k: int, subpel: int, mbinfo: torch.Tensor,
+                 mv: torch.Tensor, waves: int = 0):
+    """The in-loop deblocking filter (8.7; rule of sdv_hip_h264_lf.h) on the reconstruction planes of the pictures at position ``k`` of
+    every GOP, in place (``torch.ops.sdv.k_h264_deblock`` -> sdv_h264_deblock), from the side information ``mbinfo`` and the vectors
+    ``mv`` (even whole samples with ``subpel`` 0, quarter samples else).  Enqueue it after the encode launch of position ``k`` and before
+    that of ``k + 1``.  ``waves`` 0 is the default workgroup size, 1 .. 16 explicit; the result does not depend on it."""
+    _k_h264_deblock(ry, rcb, rcr, int(qp), int(gop), int(k), int(subpel), mbinfo, mv, int(waves))
 
 
 def _h264_pack_impl(scratch, n, mbh, mbw, out, offsets):

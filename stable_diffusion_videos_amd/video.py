@@ -18,7 +18,9 @@ the music video still carries its music; entropy-coded H.264 and AAC need ffmpeg
 names the range (``"h264 (CAVLC, gop N, search R)"``, ``LAST_CODEC["search"]``); ``h264_subpel`` 1, 2 or 4 (``pipe.h264_subpel``,
 ``SDV_H264_SUBPEL``) on top of that puts the vectors on the whole-, half- or quarter-sample grid (``"... search R, subpel S)"``,
 ``LAST_CODEC["subpel"]``); ``h264_intra4`` 1 (``pipe.h264_intra4``, ``SDV_H264_INTRA4``; at any ``h264_gop``) codes the IDR pictures
-with Intra4x4 prediction (``" + intra4"`` behind the name, ``LAST_CODEC["intra4"]``).
+with Intra4x4 prediction (``" + intra4"`` behind the name, ``LAST_CODEC["intra4"]``); ``h264_deblock`` 1 (``pipe.h264_deblock``,
+``SDV_H264_DEBLOCK``; with every other setting) switches the in-loop deblocking filter on (``" + deblock"`` behind the name,
+``LAST_CODEC["deblock"]``).
 Frames are read once each (the reference's pairwise ``torch.cat``
 is O(n^2), :91-93).
 """
@@ -231,7 +233,7 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
                     audio_offset: int = 0, audio_duration: int = 2, sr: int = 22050,
                     output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png", codec: Optional[str] = None,
                     h264_qp: Optional[int] = None, h264_gop: Optional[int] = None, h264_search: Optional[int] = None,
-                    h264_subpel: Optional[int] = None, h264_intra4: Optional[int] = None):
+                    h264_subpel: Optional[int] = None, h264_intra4: Optional[int] = None, h264_deblock: Optional[int] = None):
     """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it.  ``codec``: what
     ``SDV_VIDEO_CODEC`` selects (the variable wins): ``"h264"`` (I_PCM), ``"mjpeg"`` or ``"h264-cavlc"`` - the entropy-coded intra
     stream of h264_cavlc.py at quantiser ``h264_qp`` (0 .. 51, default 16), compressed in GPU memory; ``h264_gop``
@@ -239,7 +241,8 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     ``h264_search`` (even, 0 .. 16, default 0) > 0 motion-compensates those P pictures with whole-sample vectors of at most that many
     luma samples a component (no effect with ``h264_gop`` 1); ``h264_subpel`` (0, 1, 2 or 4, default 0) > 0 lets those vectors be any
     whole sample (1), half samples (2) or quarter samples (4) (no effect unless ``h264_gop`` > 1 and ``h264_search`` > 0);
-    ``h264_intra4`` (0 or 1, default 0) 1 codes the IDR pictures with Intra4x4 prediction (``I_NxN`` against Intra16x16 per macroblock)."""
+    ``h264_intra4`` (0 or 1, default 0) 1 codes the IDR pictures with Intra4x4 prediction (``I_NxN`` against Intra16x16 per macroblock);
+    ``h264_deblock`` (0 or 1, default 0) 1 switches the in-loop deblocking filter on (P pictures then predict from filtered pictures)."""
     output_filepath = str(output_filepath)
     gpu_frames = None                      # a uint8 tensor in GPU memory: a Motion-JPEG track is compressed there (jpeg.py)
     if isinstance(frames_or_frame_dir, torch.Tensor) and frames_or_frame_dir.is_cuda and frames_or_frame_dir.dtype == torch.uint8 \
@@ -287,6 +290,8 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
         subpel = check_subpel(DEFAULT_SUBPEL if h264_subpel is None else h264_subpel)
         from .h264_cavlc import DEFAULT_INTRA4, check_intra4
         intra4 = check_intra4(DEFAULT_INTRA4 if h264_intra4 is None else h264_intra4)
+        from .h264_cavlc import DEFAULT_DEBLOCK, check_deblock
+        deblock = check_deblock(DEFAULT_DEBLOCK if h264_deblock is None else h264_deblock)
         if h % 2 or w % 2:
             codec = "h264"                                                                     # (the odd-size rule below sends it to Motion-JPEG)
         elif gpu_frames is not None:
@@ -329,10 +334,13 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     if codec == "h264-cavlc" and intra4:
         LAST_CODEC["video"] += " + intra4"
         LAST_CODEC["intra4"] = intra4
+    if codec == "h264-cavlc" and deblock:
+        LAST_CODEC["video"] += " + deblock"
+        LAST_CODEC["deblock"] = deblock
     if codec == "h264-cavlc":
         from .h264_cavlc import encoder_for as h264_encoder_for
         active = gop > 1 and search > 0                                                    # subpel takes effect only on searched P pictures
-        enc = h264_encoder_for(qp, cavlc_device, gop, search if gop > 1 else 0, subpel if active else 0, intra4)
+        enc = h264_encoder_for(qp, cavlc_device, gop, search if gop > 1 else 0, subpel if active else 0, intra4, deblock)
         step = max(1, H264_BATCH_BYTES // (h * w * 3))                                      # batches of about 64 MB of raw frames
         step = max(gop, step // gop * gop)                                                  # whole GOPs: the file does not depend on it
         sync: Optional[List[int]] = [] if gop > 1 else None

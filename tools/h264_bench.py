@@ -2,6 +2,7 @@
 
     python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N [--search R[,R...] [--subpel S[,S...]]]]
     python tools/h264_bench.py [--out FILE] [--reps 5] --gop N[,N...] --search R[,R...] --intra4 0,1
+    python tools/h264_bench.py [--out FILE] [--reps 5] --gop N --search R[,R...] --qp Q[,Q...] --deblock 0,1
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -34,6 +35,12 @@ tool measures Intra4x4 prediction in the IDR pictures (h264_cavlc.H264Encoder(go
 frames, the sdv_h264_encode_idr4 launch alone, and for I = 1 (512 x 512 sets, at the first N) the share of I_NxN macroblocks and the mode
 histogram of picture 0, read from its bytes by tests/h264_i4_ref.py's decoder.  Frame sets: the tiny pipeline's frames (128 x 512 x 512,
 and 8 x 2048 x 2048 through the x4 upsampler) and 48 x 512 x 512 frames of every kind of tests/h264_i4_ref.py.
+With ``--deblock D[,D...]`` (each D 0 or 1; one ``--gop``, ``--search`` a list, ``--qp Q[,Q...]`` the quantisers, default 16) the tool
+measures the in-loop deblocking filter (h264_cavlc.H264Encoder(qp=Q, gop=N, search=R, deblock=D)): per frame set one row per (Q, R, D) -
+D = 0 is the comparison of the same run: encode() ms and frames/s, bytes per frame, Y-PSNR of the returned reconstruction of all frames
+against the source, and for D = 1 one sdv_h264_deblock launch alone (position 0: one picture of every GOP) and the filter launches' share
+of encode().  Frame sets: the tiny pipeline's frames (128 x 512 x 512, and 8 x 2048 x 2048 through the x4 upsampler) and 48 x 512 x 512
+frames of the synthetic kinds ``fade``, ``pan2``, ``glyphs``, ``vramp`` and ``noise``.
 There is no fallback: without a GPU this tool fails.
 """
 from __future__ import annotations
@@ -275,6 +282,63 @@ def measure_intra4(name: str, frames, gops, searches, intra4s, reps: int) -> lis
     return rows
 
 
+def measure_deblock(name: str, frames: torch.Tensor, gop: int, searches, qps, deblocks, reps: int) -> list:
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    n, H, W, _ = frames.shape
+    y = hip.h264_planes(frames)[0]
+    rows = []
+    for qp in qps:
+        for search in searches:
+            for deblock in deblocks:
+                enc = H264Encoder(qp, frames.device, gop=gop, search=search, deblock=deblock)
+                ev, wall = timed(lambda: enc.encode(frames), reps)
+                samples, recon = enc.encode(frames, return_recon=True)
+                mse = float(((recon[0][:, :H, :W].to(torch.float64) - y[:, :H, :W].to(torch.float64)) ** 2).mean())
+                row = dict(content=name, n=n, H=H, W=W, qp=qp, gop=gop, search=search, deblock=deblock, encode_ms_events=round(ev, 3),
+                           encode_ms_host_clock=round(wall, 3), frames_per_sec=round(n / wall * 1e3, 1),
+                           bytes_per_frame=int(sum(len(s) for s in samples) // n), y_psnr_db=round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None)
+                if deblock:
+                    ws = next(iter(enc._ws.values()))
+                    ms = timed(lambda: hip.h264_deblock(*recon, qp, gop, 0, 0, ws["mbinfo"], ws["mv"]), reps)[0]
+                    launches = min(gop, n) - 1                                      # encode() leaves out the last position's filter
+                    row.update(deblock_kernel_ms=round(ms, 3), deblock_launches=launches, deblock_share_of_encode=round(ms * launches / ev, 3))
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+                del enc, recon
+                torch.cuda.empty_cache()
+    return rows
+
+
+def main_deblock(args):
+    import h264_i4_ref as I4
+    import h264_me_ref as ME
+    from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
+    from stable_diffusion_videos_amd.upsampling import RealESRGANModel
+    dev = torch.device("cuda", 0)
+    result = dict(tool=f"tools/h264_bench.py --gop {args.gop} --search {args.search} --qp {args.qp} --deblock {args.deblock}",
+                  gpu=torch.cuda.get_device_name(0), host=platform.processor() or platform.machine(), reps=args.reps, rows=[])
+    pipe = StableDiffusionWalkPipeline.from_pretrained("tiny").to(dev)
+    small = pipeline_frames(pipe, 128)
+    up = RealESRGANModel.from_pretrained("nateraw/real-esrgan")
+    up.to(dev)
+    big = torch.cat([up.upsample_u8(small[k:k + 2]) for k in range(0, 8, 2)])
+    del pipe, up
+    sets = [("tiny pipeline", lambda: small.contiguous()), ("tiny pipeline x4 upsampler", lambda: big.contiguous())]
+    for kind in ("fade", "pan2"):
+        sets.append((kind, lambda kind=kind: torch.from_numpy(ME.make_frames(kind, 48, 512, 512)).to(dev).contiguous()))
+    for kind in ("glyphs", "vramp", "noise"):
+        sets.append((kind, lambda kind=kind: torch.from_numpy(I4.make_frames(kind, 48, 512, 512)).to(dev).contiguous()))
+    for name, make in sets:
+        result["rows"] += measure_deblock(name, make(), args.gops[0], args.searches, args.qps, args.deblocks, args.reps)
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    print(line)
+
+
 def main_intra4(args):
     import h264_i4_ref as I4
     from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
@@ -350,7 +414,24 @@ def main():
     ap.add_argument("--search", default=None, help="with --gop N: R[,R...] (even, 0 .. 16): one row per motion search range, 0 = none")
     ap.add_argument("--subpel", default=None, help="with --gop N --search R (one R > 0): S[,S...] (0, 1, 2, 4): one row per vector grid, 0 = even samples")
     ap.add_argument("--intra4", default=None, help="I[,I...] (0, 1): one row per (gop, search, I); --gop and --search are then lists, 0 = Intra16x16 only")
+    ap.add_argument("--deblock", default=None, help="D[,D...] (0, 1): one row per (qp, search, D) at one --gop N; 0 = the loop filter off")
+    ap.add_argument("--qp", default=None, help="with --deblock: Q[,Q...] (0 .. 51), default 16")
     args = ap.parse_args()
+    if args.qp is not None and args.deblock is None:
+        raise SystemExit("--qp goes with --deblock (the other measurements are taken at qp 16)")
+    if args.deblock is not None:
+        args.gops = [int(v) for v in args.gop.split(",")]
+        args.searches = [int(v) for v in (args.search or "0").split(",")]
+        args.search, args.qp = args.search or "0", args.qp or "16"
+        args.qps = [int(v) for v in args.qp.split(",")]
+        args.deblocks = [int(v) for v in args.deblock.split(",")]
+        if args.subpel is not None or args.intra4 is not None or len(args.gops) != 1 or not 1 <= args.gops[0] <= 256 \
+                or any(v % 2 or not 0 <= v <= 16 for v in args.searches) or any(not 0 <= v <= 51 for v in args.qps) or any(v not in (0, 1) for v in args.deblocks):
+            raise SystemExit("--deblock takes 0 and 1, with one --gop N (1 .. 256), --search R[,R...] (even, 0 .. 16) and --qp Q[,Q...] (0 .. 51), "
+                             "without --subpel and --intra4")
+        if not torch.cuda.is_available():
+            raise SystemExit("h264_bench needs the GPU (no fallback)")
+        return main_deblock(args)
     if args.intra4 is not None:
         args.gops = [int(v) for v in args.gop.split(",")]
         args.searches = [int(v) for v in (args.search or "0").split(",")]
