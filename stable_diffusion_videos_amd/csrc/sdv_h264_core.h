@@ -1527,3 +1527,272 @@ inline void h264_lf_picture(uint8_t* ry, uint8_t* rcb, uint8_t* rcr, int mbh, in
             }
         }
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Macroblock partitions (sdv_hip_h264_part.h "H.264 partitions"): four vectors per inter macroblock, one per 8x8 luma quadrant
+// (mbPartIdx 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right), always in QUARTER samples; P_8x8 with four P_L0_8x8 sub types
+// where they differ, today's P_Skip / P_L0_16x16 where they are equal.  The pieces below are what the search kernel, the per-position
+// kernel, the filter and the host share: the admission of a vector at every subpel (0 included), the per-partition clamped windows
+// (read through the interpolators above), the vector prediction of 8.4.1.3 for 8x8 partitions in this slice layout, the macroblock
+// writer, the search's decision, and bS with four vectors a side.  Nothing above is touched.
+// ------------------------------------------------------------------------------------------------------------------------------------
+enum { kH264PartLumaWin = 13, kH264PartChromaWin = 5 }; // a partition's windows: 8 + 5 luma rows / columns, 4 + 1 chroma
+enum { kH264LfZeroPart0 = 1 << 19 };                    // bits 19 .. 22: the coded vector of partition i is (0, 0) whatever ``mv`` holds
+
+H264_HD bool h264_part_subpel_ok(int subpel) { return subpel == 0 || h264_subpel_ok(subpel); }
+// A vector (quarter samples) the rule admits for macroblock (mx, my) - the macroblock's own 16x16 rule, for every partition.  subpel 0:
+// every component a multiple of 8 (the even whole-sample grid of sdv_hip_ext.h); 1, 2, 4: h264_sub_valid.
+H264_HD bool h264_part_valid(int vx, int vy, int search, int subpel, int mx, int my, int mbw, int mbh) {
+    if (subpel == 0) return !(vx & 7) && !(vy & 7) && h264_sub_valid(vx, vy, search, 1, mx, my, mbw, mbh);
+    return h264_sub_valid(vx, vy, search, subpel, mx, my, mbw, mbh);
+}
+// The vector that is coded for a partition (the given one when it is valid, else (0, 0)), split as h264_sub_fetch splits it.
+H264_HD h264_sub_ref h264_part_fetch(int vx, int vy, int search, int subpel, int mx, int my, int mbw, int mbh) {
+    const bool ok = h264_part_valid(vx, vy, search, subpel, mx, my, mbw, mbh);
+    return h264_sub_fetch(ok ? vx : 0, ok ? vy : 0, search, 4, mx, my, mbw, mbh);   // (a valid vector lies on the quarter grid too)
+}
+// Sample i of partition ``part``'s clamped window: luma (row i / 13, column i % 13) of the 13 x 13 samples that start two before the
+// displaced 8x8 block's integer position, chroma (i / 5, i % 5) of the 5 x 5 that start at the displaced 4x4 block.  Offsets into the plane.
+H264_HD long long h264_part_luma_at(const h264_sub_ref& at, int part, int i, int mx, int my, int mbw, int mbh) {
+    const int py = h264_sub_clampi(16 * my + 8 * (part >> 1) + at.iy - 2 + i / kH264PartLumaWin, 16 * mbh - 1);
+    const int px = h264_sub_clampi(16 * mx + 8 * (part & 1) + at.ix - 2 + i % kH264PartLumaWin, 16 * mbw - 1);
+    return (long long)py * (16LL * mbw) + px;
+}
+H264_HD long long h264_part_chroma_at(const h264_sub_ref& at, int part, int i, int mx, int my, int mbw, int mbh) {
+    const int py = h264_sub_clampi(8 * my + 4 * (part >> 1) + at.ciy + i / kH264PartChromaWin, 8 * mbh - 1);
+    const int px = h264_sub_clampi(8 * mx + 4 * (part & 1) + at.cix + i % kH264PartChromaWin, 8 * mbw - 1);
+    return (long long)py * (8LL * mbw) + px;
+}
+// Prediction sample (x, y) of the MACROBLOCK (luma 0 .. 15, chroma 0 .. 7) from the four staged windows of its partitions
+// (wy: [4][13 x 13], wc: [4][5 x 5] of one component), at: the four fetched vectors
+H264_HD int h264_part_pred_luma(const uint8_t* wy, const h264_sub_ref* at, int x, int y) {
+    const int part = 2 * (y >> 3) + (x >> 3);
+    return h264_sub_luma(wy + part * kH264PartLumaWin * kH264PartLumaWin + ((y & 7) + 2) * kH264PartLumaWin + (x & 7) + 2, kH264PartLumaWin,
+                         at[part].xf, at[part].yf);
+}
+H264_HD int h264_part_pred_chroma(const uint8_t* wc, const h264_sub_ref* at, int x, int y) {
+    const int part = 2 * (y >> 2) + (x >> 2);
+    return h264_sub_chroma(wc + part * kH264PartChromaWin * kH264PartChromaWin + (y & 3) * kH264PartChromaWin + (x & 3), kH264PartChromaWin,
+                           at[part].cxf, at[part].cyf);
+}
+
+// What a macroblock hands to its right neighbour for 8.4.1.3: the vectors of its partitions 1 (v[0], neighbour A of the right macroblock's
+// partition 0 and of a 16x16 block) and 3 (v[1], neighbour A of its partition 2); both (0, 0) after P_Skip, an intra or I_PCM macroblock
+// and at the start of a row - refIdx -1 or absent, which this slice layout never needs to tell from a zero vector (see the header).
+struct h264_part_chain {
+    int v[2][2];
+};
+H264_HD int h264_part_median(int a, int b, int c) { return a > b ? (b > c ? b : a > c ? c : a) : (a > c ? a : b > c ? c : b); }
+// mvp of the four partitions from the chain and the macroblock's own vectors v[part][x / y] (partition i reads partitions < i only)
+H264_HD void h264_part_mvp(const h264_part_chain& left, const int (*v)[2], int part, int* px, int* py) {
+    if (part == 0) *px = left.v[0][0], *py = left.v[0][1];
+    else if (part == 1) *px = v[0][0], *py = v[0][1];
+    else if (part == 2) *px = h264_part_median(left.v[1][0], v[0][0], v[1][0]), *py = h264_part_median(left.v[1][1], v[0][1], v[1][1]);
+    else *px = h264_part_median(v[2][0], v[1][0], v[0][0]), *py = h264_part_median(v[2][1], v[1][1], v[0][1]);
+}
+H264_HD bool h264_part_equal(const int (*v)[2]) {
+    return v[1][0] == v[0][0] && v[2][0] == v[0][0] && v[3][0] == v[0][0] && v[1][1] == v[0][1] && v[2][1] == v[0][1] && v[3][1] == v[0][1];
+}
+
+// macroblock_layer() of a P_8x8 macroblock up to and including the luma residual: mb_type ue(3), four sub_mb_type ue(0) (P_L0_8x8), no
+// ref_idx (one active reference), the four mvd_l0 pairs, coded_block_pattern by the inter column, mb_qp_delta only with cbp != 0
+template <class Sink>
+H264_HD void h264_part_code_inter(const int16_t* lev, int cbp_luma, int cbp_chroma, const h264_chain& left, const int (*mvd)[2], Sink& s, uint8_t* tcy) {
+    h264_put_ue(s, 3u);                                 // mb_type P_8x8
+    for (int i = 0; i < 4; ++i) h264_put_ue(s, 0u);     // sub_mb_type P_L0_8x8
+    for (int i = 0; i < 4; ++i) h264_put_se(s, mvd[i][0]), h264_put_se(s, mvd[i][1]);
+    h264_put_ue(s, (unsigned)h264_cbp_inter_code(cbp_luma + 16 * cbp_chroma));
+    if (cbp_luma || cbp_chroma) h264_put_se(s, 0);      // mb_qp_delta
+    for (int b = 0; b < 16; ++b) {
+        if (!((cbp_luma >> (b >> 2)) & 1)) continue;
+        const int bx = 2 * ((b >> 2) & 1) + (b & 1), by = 2 * (b >> 3) + ((b >> 1) & 1);
+        const int a = bx ? tcy[by * 4 + bx - 1] : left.have ? left.tcy[by] : -1;
+        const int t = by ? tcy[(by - 1) * 4 + bx] : -1;
+        tcy[by * 4 + bx] = (uint8_t)h264_code_block(lev + (1 + b) * 16, 16, h264_nc(a, t), s);
+    }
+}
+template <class Sink>
+H264_HD void h264_part_code_mb(const int16_t* lev, int cbp_luma, int cbp_chroma, const h264_chain& left, const int (*mvd)[2], Sink& s, uint8_t* tcy,
+                               uint8_t* tcc) {
+    for (int i = 0; i < 16; ++i) tcy[i] = 0;            // [by * 4 + bx]
+    for (int i = 0; i < 8; ++i) tcc[i] = 0;             // [c * 4 + by * 2 + bx]
+    h264_part_code_inter(lev, cbp_luma, cbp_chroma, left, mvd, s, tcy);
+    h264_gop_code_chroma(lev, cbp_chroma, left, s, tcc);
+}
+
+// serial: h264_gop_serial_sub with four vectors v[part] (quarter samples, already through h264_part_fetch; mb->fy / fc hold the
+// per-partition prediction).  Four equal vectors, and every macroblock that is not inter, go through h264_gop_serial_sub itself with the
+// chain's partition-1 vector as the predictor: today's bits.  Otherwise P_8x8; the counting pass includes its real syntax bits.
+H264_HD void h264_gop_serial_part(h264_gop_mb* mb, unsigned nz, bool any_cdc, bool inter, bool p_slice, h264_chain& ch, h264_part_chain& pc,
+                                  const int (*v)[2], h264_writer& w, int* skip_run) {
+    if (!inter || h264_part_equal(v)) {
+        h264_mv_chain mvc;
+        mvc.vx = pc.v[0][0], mvc.vy = pc.v[0][1];
+        h264_gop_serial_sub(mb, nz, any_cdc, inter, p_slice, ch, mvc, v[0][0], v[0][1], w, skip_run);
+        pc.v[0][0] = pc.v[1][0] = mvc.vx, pc.v[0][1] = pc.v[1][1] = mvc.vy;
+        return;
+    }
+    int cbp_luma = 0;
+    for (int i = 0; i < 4; ++i)
+        if (nz & (0xfu << (4 * i))) cbp_luma |= 1 << i;
+    const int cbp_chroma = (nz & 0xff0000u) ? 2 : any_cdc ? 1 : 0;
+    int mvd[4][2];
+    for (int i = 0; i < 4; ++i) {
+        int px, py;
+        h264_part_mvp(pc, v, i, &px, &py);
+        mvd[i][0] = v[i][0] - px, mvd[i][1] = v[i][1] - py;
+    }
+    h264_put_ue(w, (unsigned)*skip_run);                // mb_skip_run (P_8x8 exists in P slices only)
+    *skip_run = 0;
+    uint8_t tcy[16], tcc[8];
+    h264_counter cnt;
+    cnt.bits = 0, cnt.failed = false;
+    h264_part_code_mb(mb->lev, cbp_luma, cbp_chroma, ch, mvd, cnt, tcy, tcc);
+    if (cnt.failed || cnt.bits > 3200) {                // Annex A.3.1 / level_prefix <= 15: I_PCM
+        h264_put_ue(w, 30u);
+        while (w.n) w.put(0u, 1);                       // pcm_alignment_zero_bit
+        for (int i = 0; i < 256; ++i) w.put(mb->sy[i], 8);
+        for (int i = 0; i < 128; ++i) w.put(mb->sc[i], 8);
+        for (int i = 0; i < 4; ++i) ch.tcy[i] = 16;
+        ch.tcc[0][0] = ch.tcc[0][1] = ch.tcc[1][0] = ch.tcc[1][1] = 16;
+        mb->mode = kH264ModePcm;
+        pc.v[0][0] = pc.v[0][1] = pc.v[1][0] = pc.v[1][1] = 0;
+        return;
+    }
+    h264_part_code_mb(mb->lev, cbp_luma, cbp_chroma, ch, mvd, w, tcy, tcc);
+    for (int i = 0; i < 4; ++i) ch.tcy[i] = tcy[i * 4 + 3];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 2; ++i) ch.tcc[c][i] = tcc[c * 4 + i * 2 + 1];
+    mb->mode = kH264ModeInter;
+    pc.v[0][0] = v[1][0], pc.v[0][1] = v[1][1], pc.v[1][0] = v[3][0], pc.v[1][1] = v[3][1];
+}
+
+// mbinfo word with four vectors: h264_lf_word (bit 18: all four coded vectors are (0, 0)) plus bits 19 .. 22 for an inter or skipped macroblock
+H264_HD uint32_t h264_part_lf_word(int mode, unsigned nz, const int (*v)[2]) {
+    uint32_t word = h264_lf_word(mode, nz, v[0][0] | v[1][0] | v[2][0] | v[3][0], v[0][1] | v[1][1] | v[2][1] | v[3][1]);
+    if (!(word & (uint32_t)kH264LfIntra))
+        for (int i = 0; i < 4; ++i)
+            if (!v[i][0] && !v[i][1]) word |= (uint32_t)kH264LfZeroPart0 << i;
+    return word;
+}
+
+// h264_gop_encode_mb_sub with four vectors: mb->sy / sc are loaded, and in a P picture the windows wy (4 x 13 x 13) and wc (2 x 4 x 5 x 5)
+// through h264_part_luma_at / h264_part_chroma_at; leaves mb->ry / rc.  Returns the macroblock's side information word.  (Host; the
+// kernel spreads the per-sample pieces over its lanes.)
+inline uint32_t h264_gop_encode_mb_part(h264_gop_mb* mb, h264_chain& ch, h264_part_chain& pc, bool p_slice, int qp, const h264_sub_ref* at,
+                                        const uint8_t* wy, const uint8_t* wc, h264_writer& w, int* skip_run) {
+    int v[4][2];
+    for (int i = 0; i < 4; ++i) v[i][0] = at[i].vx, v[i][1] = at[i].vy;
+    if (p_slice) {
+        for (int i = 0; i < 256; ++i) mb->fy[i] = (uint8_t)h264_part_pred_luma(wy, at, i & 15, i >> 4);
+        for (int i = 0; i < 128; ++i)
+            mb->fc[i] = (uint8_t)h264_part_pred_chroma(wc + (i >> 6) * 4 * kH264PartChromaWin * kH264PartChromaWin, at, i & 7, (i >> 3) & 7);
+    }
+    h264_gop_pred(mb, ch);
+    bool inter = false;
+    if (p_slice) {
+        int si = 0, sp = 0;
+        for (int b = 0; b < 16; ++b) {
+            int a, c;
+            h264_gop_block_sad(mb, b, &a, &c);
+            si += a, sp += c;
+        }
+        inter = !(si < sp);
+    }
+    unsigned nz = 0;
+    for (int b = 0; b < 24; ++b)
+        if (h264_gop_block_forward(mb, b, inter, qp)) nz |= 1u << b;
+    const bool any_cdc = h264_gop_dc(mb, inter, qp);
+    h264_gop_serial_part(mb, nz, any_cdc, inter, p_slice, ch, pc, v, w, skip_run);
+    const uint32_t word = h264_part_lf_word(mb->mode, nz, v);
+    for (int b = 0; b < 24; ++b) h264_gop_block_recon(mb, b, qp);
+    h264_gop_chain(mb, ch);
+    return word;
+}
+
+// The search's decision: the four quadrant winners are taken iff sum cost8_q + 8 lambda < cost16(w16) (strict; 8 = the extra syntax bits
+// of P_8x8 against P_L0_16x16).  Keys are h264_sub_key words.  out[part]: the vectors to write.
+H264_HD bool h264_part_decide(const unsigned long long* key8, unsigned long long key16, int lambda, int (*out)[2]) {
+    int c16, x16, y16, sum = 8 * lambda, q[4][2];
+    h264_sub_unkey(key16, &c16, &x16, &y16);
+    for (int i = 0; i < 4; ++i) {
+        int c;
+        h264_sub_unkey(key8[i], &c, &q[i][0], &q[i][1]);
+        sum += c;
+    }
+    const bool take = sum < c16;
+    for (int i = 0; i < 4; ++i) out[i][0] = take ? q[i][0] : x16, out[i][1] = take ? q[i][1] : y16;
+    return take;
+}
+
+// One side of an edge with four vectors: the word and the partitions' vectors in quarter samples ((0, 0) for an intra macroblock, under
+// bit 18, and for partition i under bit 19 + i).  ``v``: the macroblock's [4][2] of the mv tensor.
+struct h264_part_side {
+    uint32_t info;
+    int v[4][2];
+};
+H264_HD h264_part_side h264_part_side_of(uint32_t info, const int16_t* v) {
+    h264_part_side s;
+    const bool zero = (info & (uint32_t)(kH264LfIntra | kH264LfZeroMv)) != 0;
+    s.info = info;
+    for (int i = 0; i < 4; ++i) {
+        const bool z = zero || ((info >> (19 + i)) & 1u);
+        s.v[i][0] = z ? 0 : (int)v[2 * i], s.v[i][1] = z ? 0 : (int)v[2 * i + 1];
+    }
+    return s;
+}
+H264_HD int h264_part_of_block(int blk) { return 2 * (blk >> 3) + ((blk >> 1) & 1); }   // blk = 4 by + bx
+// h264_lf_bs with the vectors of the partitions that blocks pblk and qblk lie in
+H264_HD int h264_part_bs(const h264_part_side& p, int pblk, const h264_part_side& q, int qblk, bool mb_edge) {
+    if ((p.info | q.info) & (uint32_t)kH264LfIntra) return mb_edge ? 4 : 3;
+    if (((p.info >> pblk) | (q.info >> qblk)) & 1u) return 2;
+    const int* a = p.v[h264_part_of_block(pblk)];
+    const int* b = q.v[h264_part_of_block(qblk)];
+    const int dx = a[0] - b[0], dy = a[1] - b[1];
+    return (dx >= 4 || dx <= -4 || dy >= 4 || dy <= -4) ? 1 : 0;
+}
+H264_HD int h264_part_index(const h264_part_side& p, const h264_part_side& q, int qp, bool chroma) {
+    h264_lf_side a, b;
+    a.info = p.info, b.info = q.info, a.vx = a.vy = b.vx = b.vy = 0;
+    return h264_lf_index(a, b, qp, chroma);
+}
+// h264_lf_luma_line / h264_lf_chroma_line with four vectors a side
+H264_HD void h264_part_luma_line(uint8_t* mb, int stride, int dir, int e, int l, const h264_part_side& p, const h264_part_side& q, int qp) {
+    const int along = l >> 2, pe = e ? e - 1 : 3;
+    const int qblk = dir ? 4 * e + along : 4 * along + e, pblk = dir ? 4 * pe + along : 4 * along + pe;
+    const int bS = h264_part_bs(p, pblk, q, qblk, e == 0);
+    if (!bS) return;
+    h264_lf_line(dir ? mb + 4 * e * stride + l : mb + l * stride + 4 * e, dir ? stride : 1, bS, h264_part_index(p, q, qp, false), false);
+}
+H264_HD void h264_part_chroma_line(uint8_t* mb, int stride, int dir, int c, int l, const h264_part_side& p, const h264_part_side& q, int qp) {
+    const int e = 2 * c, along = l >> 1, pe = e ? e - 1 : 3;
+    const int qblk = dir ? 4 * e + along : 4 * along + e, pblk = dir ? 4 * pe + along : 4 * along + pe;
+    const int bS = h264_part_bs(p, pblk, q, qblk, e == 0);
+    if (!bS) return;
+    h264_lf_line(dir ? mb + 4 * c * stride + l : mb + l * stride + 4 * c, dir ? stride : 1, bS, h264_part_index(p, q, qp, true), true);
+}
+// h264_lf_picture with four vectors a macroblock (host).  info [mbh * mbw], mv [mbh * mbw * 8].
+inline void h264_part_lf_picture(uint8_t* ry, uint8_t* rcb, uint8_t* rcr, int mbh, int mbw, int qp, const uint32_t* info, const int16_t* mv) {
+    const int lw = 16 * mbw, cw = 8 * mbw;
+    for (int my = 0; my < mbh; ++my)
+        for (int mx = 0; mx < mbw; ++mx) {
+            const int at = my * mbw + mx;
+            const h264_part_side q = h264_part_side_of(info[at], mv + 8 * at);
+            const h264_part_side left = mx ? h264_part_side_of(info[at - 1], mv + 8 * (at - 1)) : q;
+            const h264_part_side up = my ? h264_part_side_of(info[at - mbw], mv + 8 * (at - mbw)) : q;
+            uint8_t* y0 = ry + (long long)my * 16 * lw + mx * 16;
+            for (int dir = 0; dir < 2; ++dir)
+                for (int e = 0; e < 4; ++e) {
+                    if (e == 0 && !(dir ? my : mx)) continue;
+                    for (int l = 0; l < 16; ++l) h264_part_luma_line(y0, lw, dir, e, l, e ? q : dir ? up : left, q, qp);
+                }
+            for (int c = 0; c < 2; ++c) {
+                uint8_t* c0 = (c ? rcr : rcb) + (long long)my * 8 * cw + mx * 8;
+                for (int dir = 0; dir < 2; ++dir)
+                    for (int e = 0; e < 2; ++e) {
+                        if (e == 0 && !(dir ? my : mx)) continue;
+                        for (int l = 0; l < 8; ++l) h264_part_chroma_line(c0, cw, dir, e, l, e ? q : dir ? up : left, q, qp);
+                    }
+            }
+        }
+}

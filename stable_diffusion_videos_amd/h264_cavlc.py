@@ -31,6 +31,12 @@ information word per macroblock, and a filter launch between two positions rewri
 predict from filtered pictures.  tests/h264_lf_ref.py restates, decodes and filters it.  ``deblock`` 0 is the code and the bytes of the
 other settings alone.
 
+``part`` 1 (opt-in on top of ``gop`` > 1 and ``search`` > 0, with every ``subpel``, ``intra4`` and ``deblock``; include/sdv_hip_h264_part.h and
+DESIGN.md "H.264 partitions") gives every inter macroblock four vectors, one per 8x8 quadrant: the search keeps the four quadrant winners
+beside the 16x16 one and takes them where they are cheaper by more than their syntax, ``P_8x8`` macroblocks carry them, prediction is per
+partition and the loop filter compares the vectors per partition.  tests/h264_part_ref.py restates and decodes it.  ``part`` 0, or ``part``
+1 without P pictures or without a search, is the code and the bytes of the other settings alone.
+
 Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
 """
 from __future__ import annotations
@@ -47,6 +53,7 @@ DEFAULT_SEARCH = 0                                                              
 DEFAULT_SUBPEL = 0                                                                              # a setting, not a measured optimum
 DEFAULT_INTRA4 = 0                                                                              # a setting, not a measured optimum
 DEFAULT_DEBLOCK = 0                                                                             # a setting, not a measured optimum
+DEFAULT_PART = 0                                                                                # a setting, not a measured optimum
 
 
 def check_qp(qp) -> int:
@@ -85,6 +92,12 @@ def check_deblock(deblock) -> int:
     return deblock
 
 
+def check_part(part) -> int:
+    if isinstance(part, bool) or not isinstance(part, int) or part not in (0, 1):
+        raise ValueError(f"h264 part must be one of the integers 0, 1, got {part!r}")
+    return part
+
+
 class H264Encoder:
     """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
     (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.  With ``gop``
@@ -99,19 +112,23 @@ class H264Encoder:
     any ``gop``, so ``return_recon`` works at ``gop`` 1 too.  ``deblock`` 1 switches the in-loop deblocking filter on: every picture
     position through a per-position entry point (the IDR pictures through the k = 0 step, or the Intra4x4 launch), and one filter launch
     after each position but the last, whose filtered planes only ``return_recon`` reads (it then runs too); GOP workspaces at any ``gop``.
+    ``part`` 1 (no effect unless ``gop`` > 1 and ``search`` > 0) runs the partition search, then every P position - and, without ``intra4``,
+    the IDR position - through the four-vector entry points, and the four-vector filter with ``deblock``; the same number of launches.
 
     Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
     prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
     capacity bound of sdv_hip.h, so no batch can fail to fit."""
 
     def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH,
-                 subpel: int = DEFAULT_SUBPEL, intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK):
+                 subpel: int = DEFAULT_SUBPEL, intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK, part: int = DEFAULT_PART):
         self.qp = check_qp(qp)
         self.gop = check_gop(gop)
         self.search = check_search(search)
         self.subpel = check_subpel(subpel)
         self.intra4 = check_intra4(intra4)
         self.deblock = check_deblock(deblock)
+        self.part = check_part(part)
+        self._parted = self.part == 1 and self.gop > 1 and self.search > 0                      # otherwise part 1 is today's route
         self.last_sync: List[int] = []
         self.device = torch.device(device) if device is not None else None
         self._ws: Dict[tuple, dict] = {}
@@ -134,7 +151,11 @@ class H264Encoder:
                       out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True))
             if gops:                                                                            # the reference pictures stay in HBM
                 ws.update(ry=torch.empty_like(ws["y"]), rcb=torch.empty_like(ws["cb"]), rcr=torch.empty_like(ws["cr"]))
-                if self.deblock:                                                                # the filter reads the vectors of every picture
+                if self._parted:                                                                # four quarter-sample vectors a macroblock
+                    ws.update(mv=torch.zeros((n, mbh, mbw, 4, 2), dtype=torch.int16, device=device))
+                    if self.deblock:
+                        ws.update(mbinfo=torch.zeros((n, mbh, mbw), dtype=torch.int32, device=device))
+                elif self.deblock:                                                              # the filter reads the vectors of every picture
                     ws.update(mv=torch.zeros((n, mbh, mbw, 2), dtype=torch.int16, device=device),
                               mbinfo=torch.zeros((n, mbh, mbw), dtype=torch.int32, device=device))
                 elif self.search and self.gop > 1:                                              # even samples, or quarter samples with subpel
@@ -182,7 +203,10 @@ class H264Encoder:
             return self._rows_and_pack(ws, n, mbh, mbw, first_index, return_recon)
 
     def _rows_and_pack(self, ws: dict, n: int, mbh: int, mbw: int, first_index: int, return_recon: bool = False):
-        if self.deblock:
+        if self._parted:
+            self._parted_steps(ws, n, int(first_index), return_recon)
+            hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
+        elif self.deblock:
             self._deblocked_steps(ws, n, int(first_index), return_recon)
             hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
         elif self.intra4:
@@ -264,14 +288,37 @@ class H264Encoder:
                 hip.h264_deblock(*recon, self.qp, self.gop, k, sub, ws["mbinfo"], ws["mv"])
 
 
+    def _parted_steps(self, ws: dict, n: int, first_index: int, filter_last: bool):
+        """``part`` (with ``gop`` > 1 and ``search`` > 0): the partition search over all P pictures, then every picture position in order
+        through the four-vector entry points (IDR pictures through the Intra4x4 launch with ``intra4``), with the side information and
+        the four-vector filter between two positions when ``deblock`` is on."""
+        planes, recon = (ws["y"], ws["cb"], ws["cr"]), (ws["ry"], ws["rcb"], ws["rcr"])
+        last = min(self.gop, n)
+        if last > 1:
+            hip.h264_motion_search_part(ws["y"], self.qp, self.gop, self.search, self.subpel, ws["mv"])
+        for k in range(last):
+            if k == 0 and self.intra4 and self.deblock:
+                hip.h264_encode_idr4_lf(*planes, self.qp, self.gop, first_index, *recon, ws["scratch"], ws["mbinfo"])
+            elif k == 0 and self.intra4:
+                hip.h264_encode_idr4(*planes, self.qp, self.gop, first_index, *recon, ws["scratch"])
+            elif self.deblock:
+                hip.h264_encode_gop_step_part_lf(*planes, self.qp, self.gop, k, self.search, self.subpel, first_index, ws["mv"], *recon, ws["scratch"],
+                                                 ws["mbinfo"])
+            else:
+                hip.h264_encode_gop_step_part(*planes, self.qp, self.gop, k, self.search, self.subpel, first_index, ws["mv"], *recon, ws["scratch"])
+            if self.deblock and (k + 1 < last or filter_last):
+                hip.h264_deblock_part(*recon, self.qp, self.gop, k, ws["mbinfo"], ws["mv"])
+
+
 _encoders: Dict[tuple, H264Encoder] = {}
 
 
 def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH, subpel: int = DEFAULT_SUBPEL,
-                intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK) -> H264Encoder:
+                intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK, part: int = DEFAULT_PART) -> H264Encoder:
     """One cached encoder (and its workspaces) per quality setting, GOP length, search range, vector grid, intra setting, loop filter
-    setting and device."""
-    key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel), check_intra4(intra4), check_deblock(deblock))
+    setting, partition setting and device."""
+    key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel), check_intra4(intra4), check_deblock(deblock),
+           check_part(part))
     if key not in _encoders:
-        _encoders[key] = H264Encoder(qp, device, gop, search, subpel, intra4, deblock)
+        _encoders[key] = H264Encoder(qp, device, gop, search, subpel, intra4, deblock, part)
     return _encoders[key]

@@ -135,6 +135,16 @@ _H264_LF_SIGNATURES = {
     "sdv_h264_deblock": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 7 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
 }
 H264_LF_SYMBOLS = tuple(_H264_LF_SIGNATURES)
+# include/sdv_hip_h264_part.h: four vectors per macroblock (P_8x8): the search, the per-position pair and the filter, each with the element
+# count of ``mv`` (and of ``sad`` / ``mbinfo``) after its pointer
+_H264_PART_SIGNATURES = {
+    "sdv_h264_motion_search_part": (C.c_int, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sdv_h264_encode_gop_step_part": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "sdv_h264_encode_gop_step_part_lf": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 +
+                                         [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sdv_h264_deblock_part": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+}
+H264_PART_SYMBOLS = tuple(_H264_PART_SIGNATURES)
 
 
 def lib_path() -> Path:
@@ -155,7 +165,8 @@ def load(build_if_missing: bool = False):
                 f"{_LIB_PATH} is missing - build it with `python -m stable_diffusion_videos_amd.build` "
                 "(there is no CPU / eager fallback for the hot path)")
     lib = C.CDLL(str(_LIB_PATH))
-    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES, **_H264_I4_SIGNATURES, **_H264_LF_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES, **_H264_I4_SIGNATURES, **_H264_LF_SIGNATURES,
+                              **_H264_PART_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1950,6 +1961,156 @@ def h264_deblock(ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, qp: int
     ``mv`` (even whole samples with ``subpel`` 0, quarter samples else).  Enqueue it after the encode launch of position ``k`` and before
     that of ``k + 1``.  ``waves`` 0 is the default workgroup size, 1 .. 16 explicit; the result does not depend on it."""
     _k_h264_deblock(ry, rcb, rcr, int(qp), int(gop), int(k), int(subpel), mbinfo, mv, int(waves))
+
+
+# ---- macroblock partitions (include/sdv_hip_h264_part.h): four quarter-sample vectors per macroblock ----
+H264_PART_SUBPELS = (0,) + H264_SUBPELS
+
+
+def _h264_part_subpel_value(what, subpel):
+    if subpel not in H264_PART_SUBPELS:
+        raise SdvHipError(f"{what}: subpel must be 0, 1, 2 or 4, got {subpel}")
+
+
+def _h264_part_mv_check(what, mv, n, mbh, mbw):
+    """The vector tensor of sdv_hip_h264_part.h: int16 [n, mbh, mbw, 4, 2], contiguous."""
+    if not isinstance(mv, torch.Tensor) or mv.dtype != torch.int16 or not mv.is_contiguous() or tuple(mv.shape) != (n, mbh, mbw, 4, 2):
+        raise SdvHipError(f"{what}: mv must be a contiguous int16 {[n, mbh, mbw, 4, 2]} tensor, got {getattr(mv, 'dtype', type(mv))} "
+                          f"{tuple(getattr(mv, 'shape', ()))}")
+
+
+def _h264_motion_search_part_impl(y, qp, gop, search, subpel, mv, sad):
+    what = "h264_motion_search_part"
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.uint8 or y.ndim != 3 or not y.is_contiguous() or y.shape[0] < 1 \
+            or y.shape[1] % 16 or y.shape[2] % 16 or not y.shape[1] or not y.shape[2]:
+        raise SdvHipError(f"{what}: y must be a contiguous uint8 [n, 16 mbh, 16 mbw] tensor, got {getattr(y, 'dtype', type(y))} "
+                          f"{tuple(getattr(y, 'shape', ()))}")
+    n, mbh, mbw = y.shape[0], y.shape[1] // 16, y.shape[2] // 16
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    _h264_search_range(what, search)
+    _h264_part_subpel_value(what, subpel)
+    _h264_part_mv_check(what, mv, n, mbh, mbw)
+    if sad is not None and (sad.dtype != torch.int32 or not sad.is_contiguous() or tuple(sad.shape) != (n, mbh, mbw, 5)):
+        raise SdvHipError(f"{what}: sad must be a contiguous int32 {[n, mbh, mbw, 5]} tensor, got {sad.dtype} {tuple(sad.shape)}")
+    lib = load()
+    args = (_ptr(y, name="y"), n, mbh, mbw, int(qp), int(gop), int(search), int(subpel), _ptr(mv, name="mv"), mv.numel(), _ptr(sad, name="sad"),
+            0 if sad is None else sad.numel())
+    _launch("h264_motion_search_part", dict(bytes=2.0 * y.numel()),
+            lambda: _check(lib.sdv_h264_motion_search_part(*args, _stream()), "sdv_h264_motion_search_part"))
+
+
+_k_h264_motion_search_part = _defop("k_h264_motion_search_part(Tensor y, int qp, int gop, int search, int subpel, Tensor(a!) mv, Tensor(b!)? sad) -> ()",
+                                    _h264_motion_search_part_impl)
+
+
+def h264_motion_search_part(y: torch.Tensor, qp: int, gop: int, search: int, subpel: int, mv: torch.Tensor, sad: Optional[torch.Tensor] = None):
+    """``h264_motion_search_sub`` that also keeps the winner of every 8x8 quadrant and decides between them and the 16x16 winner by the
+    rule of sdv_hip_h264_part.h (``torch.ops.sdv.k_h264_motion_search_part`` -> sdv_h264_motion_search_part); ``subpel`` 0, 1, 2 or 4.
+    ``mv``: int16 ``[n, mbh, mbw, 4, 2]`` in QUARTER samples (four equal vectors where the 16x16 winner stands), zeros for IDR pictures;
+    ``sad``: int32 ``[n, mbh, mbw, 5]`` (optional), the source SADs of the four quadrant winners and of the 16x16 winner."""
+    _k_h264_motion_search_part(y, int(qp), int(gop), int(search), int(subpel), mv, sad)
+
+
+def _h264_encode_gop_step_part_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch, mbinfo=None):
+    what = "h264_encode_gop_step_part" if mbinfo is None else "h264_encode_gop_step_part_lf"
+    n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if mbinfo is not None:
+        _h264_mbinfo_check(what, mbinfo, n, mbh, mbw)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    if not 0 <= k < min(gop, n):
+        raise SdvHipError(f"{what}: position k must be 0 .. min(gop, n) - 1 = {min(gop, n) - 1}, got {k}")
+    _h264_search_range(what, search)
+    _h264_part_subpel_value(what, subpel)
+    if mbw > H264_GOP_MAX_MBW:
+        raise SdvHipError(f"{what}: pictures wider than {H264_GOP_MAX_MBW} macroblocks are not coded with P pictures, got mbw={mbw}")
+    if first_index < 0:
+        raise SdvHipError(f"{what}: first_index must be >= 0, got {first_index}")
+    _h264_part_mv_check(what, mv, n, mbh, mbw)
+    _h264_u8(what, "ry", ry, y.shape)
+    _h264_u8(what, "rcb", rcb, cb.shape)
+    _h264_u8(what, "rcr", rcr, cr.shape)
+    _h264_u8(what, "scratch", scratch)
+    need = h264_gop_scratch_bytes(n, mbh, mbw)
+    if scratch.ndim != 1 or scratch.numel() < need:
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n * mbh} slices of {mbw} macroblocks need {need}")
+    lib = load()
+    args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(k), int(search), int(subpel),
+            int(first_index) & 0x7fffffff, _ptr(mv, name="mv"), mv.numel(), _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"),
+            _ptr(scratch, name="scratch"), scratch.numel())
+    if mbinfo is not None:
+        lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+        _launch("h264_encode_gop_step_part_lf", dict(bytes=3.0 * y.numel() / min(gop, n)),
+                lambda: _check(lib.sdv_h264_encode_gop_step_part_lf(*args, *lf, _stream()), "sdv_h264_encode_gop_step_part_lf"))
+        return
+    _launch("h264_encode_gop_step_part", dict(bytes=3.0 * y.numel() / min(gop, n)),
+            lambda: _check(lib.sdv_h264_encode_gop_step_part(*args, _stream()), "sdv_h264_encode_gop_step_part"))
+
+
+def _h264_encode_gop_step_part_lf_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch, mbinfo):
+    _h264_encode_gop_step_part_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch,
+                                    _h264_mbinfo_given("h264_encode_gop_step_part_lf", mbinfo))
+
+
+def _h264_deblock_part_impl(ry, rcb, rcr, qp, gop, k, mbinfo, mv, waves):
+    what = "h264_deblock_part"
+    n, mbh, mbw = _h264_plane_grid(what, ry, rcb, rcr)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    if not 0 <= k < min(gop, n):
+        raise SdvHipError(f"{what}: position k must be 0 .. min(gop, n) - 1 = {min(gop, n) - 1}, got {k}")
+    if not 0 <= waves <= H264_LF_WAVES_MAX:
+        raise SdvHipError(f"{what}: waves must be 0 (the default) .. {H264_LF_WAVES_MAX}, got {waves}")
+    _h264_part_mv_check(what, mv, n, mbh, mbw)
+    lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+    lib = load()
+    args = (_ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"), n, mbh, mbw, int(qp), int(gop), int(k), *lf, _ptr(mv, name="mv"),
+            mv.numel(), int(waves))
+    _launch("h264_deblock_part", dict(bytes=3.0 * ry.numel() / min(gop, n)),
+            lambda: _check(lib.sdv_h264_deblock_part(*args, _stream()), "sdv_h264_deblock_part"))
+
+
+_k_h264_encode_gop_step_part = _defop("k_h264_encode_gop_step_part(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int k, int search, int subpel, "
+                                      "int first_index, Tensor mv, Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch) -> ()",
+                                      _h264_encode_gop_step_part_impl)
+_k_h264_encode_gop_step_part_lf = _defop("k_h264_encode_gop_step_part_lf(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int k, int search, int subpel, "
+                                         "int first_index, Tensor mv, Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch, "
+                                         "Tensor(e!) mbinfo) -> ()", _h264_encode_gop_step_part_lf_impl)
+_k_h264_deblock_part = _defop("k_h264_deblock_part(Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, int qp, int gop, int k, Tensor mbinfo, Tensor mv, "
+                              "int waves) -> ()", _h264_deblock_part_impl)
+
+
+def h264_encode_gop_step_part(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, k: int, search: int, subpel: int,
+                              first_index: int, mv: torch.Tensor, ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor):
+    """``h264_encode_gop_step_sub`` with the four vectors per macroblock of ``h264_motion_search_part`` (``mv`` int16 ``[n, mbh, mbw, 4, 2]``,
+    quarter samples; ``subpel`` 0, 1, 2 or 4): ``P_8x8`` where they differ, today's macroblock types where they are equal (rule of
+    sdv_hip_h264_part.h; ``torch.ops.sdv.k_h264_encode_gop_step_part`` -> sdv_h264_encode_gop_step_part).  Call it for
+    k = 0 .. min(gop, n) - 1 in order on one stream."""
+    _k_h264_encode_gop_step_part(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch)
+
+
+def h264_encode_gop_step_part_lf(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, k: int, search: int, subpel: int,
+                                 first_index: int, mv: torch.Tensor, ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor,
+                                 mbinfo: torch.Tensor):
+    """``h264_encode_gop_step_part`` for a stream with the loop filter on (``torch.ops.sdv.k_h264_encode_gop_step_part_lf`` ->
+    sdv_h264_encode_gop_step_part_lf): ``mbinfo`` takes the side information words with bits 19 .. 22; ``h264_deblock_part`` for the same
+    ``k`` follows before the next position."""
+    _k_h264_encode_gop_step_part_lf(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch,
+                                    mbinfo)
+
+
+def h264_deblock_part(ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, qp: int, gop: int, k: int, mbinfo: torch.Tensor, mv: torch.Tensor,
+                      waves: int = 0):
+    """``h264_deblock`` with four vectors per macroblock (``mv`` int16 ``[n, mbh, mbw, 4, 2]``, always quarter samples) and the side
+    information of ``h264_encode_gop_step_part_lf`` (``torch.ops.sdv.k_h264_deblock_part`` -> sdv_h264_deblock_part)."""
+    _k_h264_deblock_part(ry, rcb, rcr, int(qp), int(gop), int(k), mbinfo, mv, int(waves))
 
 
 def _h264_pack_impl(scratch, n, mbh, mbw, out, offsets):

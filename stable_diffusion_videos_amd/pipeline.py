@@ -125,6 +125,7 @@ class StableDiffusionWalkPipeline:
         self.h264_search = 0               # motion search range of its P pictures in luma samples (even, 0 .. 16; 0 = none); SDV_H264_SEARCH wins
         self.h264_subpel = 0               # grid of those vectors: 0 = even whole samples, 1 = whole, 2 = half, 4 = quarter samples; SDV_H264_SUBPEL wins
         self.h264_intra4 = 0               # 1 = its IDR pictures use Intra4x4 prediction (I_NxN against Intra16x16 per macroblock); SDV_H264_INTRA4 wins
+        self.h264_part = 0                 # 1 = its inter macroblocks may carry one vector per 8x8 quadrant (P_8x8; needs gop > 1 and search > 0); SDV_H264_PART wins
         self.h264_deblock = 0              # 1 = its in-loop deblocking filter is on (P pictures predict from filtered pictures); SDV_H264_DEBLOCK wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
@@ -721,6 +722,21 @@ class StableDiffusionWalkPipeline:
             raise ValueError(f"SDV_H264_INTRA4 / h264_intra4 must be 0 or 1, got {intra4!r}")
         return intra4
 
+    def h264_part_choice(self) -> int:
+        """Whether the ``h264-cavlc`` video track may code inter macroblocks as ``P_8x8`` with one vector per 8x8 quadrant: the environment
+        variable SDV_H264_PART (0 or 1) when it is set, else ``self.h264_part``.  0 = one vector per macroblock; a setting, not a measured
+        optimum."""
+        env = os.environ.get("SDV_H264_PART")
+        if not env:
+            part = self.h264_part
+        elif env in ("0", "1"):
+            part = int(env)
+        else:
+            raise ValueError(f"SDV_H264_PART must be 0 or 1, got {env!r}")
+        if isinstance(part, bool) or not isinstance(part, int) or part not in (0, 1):
+            raise ValueError(f"SDV_H264_PART / h264_part must be 0 or 1, got {part!r}")
+        return part
+
     def h264_deblock_choice(self) -> int:
         """Whether the ``h264-cavlc`` video track runs the in-loop deblocking filter: the environment variable SDV_H264_DEBLOCK (0 or 1)
         when it is set, else ``self.h264_deblock``.  0 = every slice switches the filter off; a setting, not a measured optimum."""
@@ -968,7 +984,8 @@ class StableDiffusionWalkPipeline:
                                 audio_duration=num_step / fps, sr=44100, codec=self.video_codec,
                                 h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice(),
                                 h264_search=self.h264_search_choice(), h264_subpel=self.h264_subpel_choice(),
-                                h264_intra4=self.h264_intra4_choice(), h264_deblock=self.h264_deblock_choice())  # :787-796
+                                h264_intra4=self.h264_intra4_choice(), h264_deblock=self.h264_deblock_choice(),
+                                h264_part=self.h264_part_choice())  # :787-796
             result = make_video_pyav(save_path_root, audio_filepath=audio_filepath, fps=fps, audio_offset=audio_start_sec,
                                      audio_duration=sum(num_interpolation_steps) / fps, output_filepath=output_filepath,
                                      glob_pattern=f"**/*{image_file_ext}", sr=44100, codec=self.video_codec,
@@ -976,7 +993,7 @@ class StableDiffusionWalkPipeline:
                                      h264_search=self.h264_search_choice(),
                                      h264_subpel=self.h264_subpel_choice(),
                                      h264_intra4=self.h264_intra4_choice(),
-                                     h264_deblock=self.h264_deblock_choice())                # :798-807
+                                     h264_deblock=self.h264_deblock_choice(), h264_part=self.h264_part_choice())                # :798-807
         if world_size > 1:
             parallel.barrier()
             result = str(output_filepath) if result is None else result

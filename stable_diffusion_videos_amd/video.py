@@ -20,7 +20,8 @@ names the range (``"h264 (CAVLC, gop N, search R)"``, ``LAST_CODEC["search"]``);
 ``LAST_CODEC["subpel"]``); ``h264_intra4`` 1 (``pipe.h264_intra4``, ``SDV_H264_INTRA4``; at any ``h264_gop``) codes the IDR pictures
 with Intra4x4 prediction (``" + intra4"`` behind the name, ``LAST_CODEC["intra4"]``); ``h264_deblock`` 1 (``pipe.h264_deblock``,
 ``SDV_H264_DEBLOCK``; with every other setting) switches the in-loop deblocking filter on (``" + deblock"`` behind the name,
-``LAST_CODEC["deblock"]``).
+``LAST_CODEC["deblock"]``); ``h264_part`` 1 (``pipe.h264_part``, ``SDV_H264_PART``; no effect unless ``h264_gop`` > 1 and ``h264_search``
+> 0) gives inter macroblocks one vector per 8x8 quadrant, ``P_8x8`` (``" + part"`` behind the name, ``LAST_CODEC["part"]``).
 Frames are read once each (the reference's pairwise ``torch.cat``
 is O(n^2), :91-93).
 """
@@ -233,7 +234,8 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
                     audio_offset: int = 0, audio_duration: int = 2, sr: int = 22050,
                     output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png", codec: Optional[str] = None,
                     h264_qp: Optional[int] = None, h264_gop: Optional[int] = None, h264_search: Optional[int] = None,
-                    h264_subpel: Optional[int] = None, h264_intra4: Optional[int] = None, h264_deblock: Optional[int] = None):
+                    h264_subpel: Optional[int] = None, h264_intra4: Optional[int] = None, h264_deblock: Optional[int] = None,
+                    h264_part: Optional[int] = None):
     """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it.  ``codec``: what
     ``SDV_VIDEO_CODEC`` selects (the variable wins): ``"h264"`` (I_PCM), ``"mjpeg"`` or ``"h264-cavlc"`` - the entropy-coded intra
     stream of h264_cavlc.py at quantiser ``h264_qp`` (0 .. 51, default 16), compressed in GPU memory; ``h264_gop``
@@ -242,7 +244,9 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     luma samples a component (no effect with ``h264_gop`` 1); ``h264_subpel`` (0, 1, 2 or 4, default 0) > 0 lets those vectors be any
     whole sample (1), half samples (2) or quarter samples (4) (no effect unless ``h264_gop`` > 1 and ``h264_search`` > 0);
     ``h264_intra4`` (0 or 1, default 0) 1 codes the IDR pictures with Intra4x4 prediction (``I_NxN`` against Intra16x16 per macroblock);
-    ``h264_deblock`` (0 or 1, default 0) 1 switches the in-loop deblocking filter on (P pictures then predict from filtered pictures)."""
+    ``h264_deblock`` (0 or 1, default 0) 1 switches the in-loop deblocking filter on (P pictures then predict from filtered pictures);
+    ``h264_part`` (0 or 1, default 0) 1 lets inter macroblocks carry one vector per 8x8 quadrant (``P_8x8``; no effect unless ``h264_gop`` >
+    1 and ``h264_search`` > 0)."""
     output_filepath = str(output_filepath)
     gpu_frames = None                      # a uint8 tensor in GPU memory: a Motion-JPEG track is compressed there (jpeg.py)
     if isinstance(frames_or_frame_dir, torch.Tensor) and frames_or_frame_dir.is_cuda and frames_or_frame_dir.dtype == torch.uint8 \
@@ -292,6 +296,8 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
         intra4 = check_intra4(DEFAULT_INTRA4 if h264_intra4 is None else h264_intra4)
         from .h264_cavlc import DEFAULT_DEBLOCK, check_deblock
         deblock = check_deblock(DEFAULT_DEBLOCK if h264_deblock is None else h264_deblock)
+        from .h264_cavlc import DEFAULT_PART, check_part
+        part = check_part(DEFAULT_PART if h264_part is None else h264_part)
         if h % 2 or w % 2:
             codec = "h264"                                                                     # (the odd-size rule below sends it to Motion-JPEG)
         elif gpu_frames is not None:
@@ -337,10 +343,13 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     if codec == "h264-cavlc" and deblock:
         LAST_CODEC["video"] += " + deblock"
         LAST_CODEC["deblock"] = deblock
+    if codec == "h264-cavlc" and part and gop > 1 and search > 0:
+        LAST_CODEC["video"] += " + part"
+        LAST_CODEC["part"] = part
     if codec == "h264-cavlc":
         from .h264_cavlc import encoder_for as h264_encoder_for
         active = gop > 1 and search > 0                                                    # subpel takes effect only on searched P pictures
-        enc = h264_encoder_for(qp, cavlc_device, gop, search if gop > 1 else 0, subpel if active else 0, intra4, deblock)
+        enc = h264_encoder_for(qp, cavlc_device, gop, search if gop > 1 else 0, subpel if active else 0, intra4, deblock, part if active else 0)
         step = max(1, H264_BATCH_BYTES // (h * w * 3))                                      # batches of about 64 MB of raw frames
         step = max(gop, step // gop * gop)                                                  # whole GOPs: the file does not depend on it
         sync: Optional[List[int]] = [] if gop > 1 else None

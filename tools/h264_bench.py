@@ -3,6 +3,7 @@
     python tools/h264_bench.py [--out FILE] [--reps 5] [--gop N [--search R[,R...] [--subpel S[,S...]]]]
     python tools/h264_bench.py [--out FILE] [--reps 5] --gop N[,N...] --search R[,R...] --intra4 0,1
     python tools/h264_bench.py [--out FILE] [--reps 5] --gop N --search R[,R...] --qp Q[,Q...] --deblock 0,1
+    python tools/h264_bench.py [--out FILE] [--reps 5] --gop N --search R --subpel S[,S...] --deblock D[,D...] --qp Q[,Q...] --part 0,1
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -41,6 +42,14 @@ D = 0 is the comparison of the same run: encode() ms and frames/s, bytes per fra
 against the source, and for D = 1 one sdv_h264_deblock launch alone (position 0: one picture of every GOP) and the filter launches' share
 of encode().  Frame sets: the tiny pipeline's frames (128 x 512 x 512, and 8 x 2048 x 2048 through the x4 upsampler) and 48 x 512 x 512
 frames of the synthetic kinds ``fade``, ``pan2``, ``glyphs``, ``vramp`` and ``noise``.
+With ``--part P[,P...]`` (each P 0 or 1; one ``--gop`` N > 1, one ``--search`` R > 0, ``--subpel S[,S...]``, ``--deblock D[,D...]`` and
+``--qp Q[,Q...]`` lists, defaults 0, 0 and 16) the tool measures macroblock partitions (h264_cavlc.H264Encoder(..., part=P)): per frame set
+one row per (Q, S, D, P) - bytes per frame, encode() ms (HIP events, the copy back included), Y-PSNR of the reconstruction, the search
+launch alone, and for P = 1 the share of the P pictures' macroblocks for which the search wrote four vectors that are not all equal (the
+P_8x8 candidates; the mode decision may still code one of them intra).  Two more synthetic kinds have motion that differs inside a
+macroblock: ``split`` (the upper 8 rows of every macroblock row glide right by 2 samples a picture, the lower 8 left) and ``zoom`` (the
+same texture magnified by 0.4 % a picture about the centre).  The P = 0 rows of a run are the comparison.
+
 There is no fallback: without a GPU this tool fails.
 """
 from __future__ import annotations
@@ -310,6 +319,89 @@ def measure_deblock(name: str, frames: torch.Tensor, gop: int, searches, qps, de
     return rows
 
 
+def zoom_frames(n: int, size: int) -> np.ndarray:
+    """tests/h264_sub_ref.py's analytic texture magnified by 0.4 % a picture about the centre: every 8x8 block moves a little differently."""
+    yy, xx = np.mgrid[0:size, 0:size].astype(np.float64)
+    c = (size - 1) / 2.0
+    frames = np.empty((n, size, size, 3), dtype=np.uint8)
+    for k in range(n):
+        x, y = c + (xx - c) / (1.0 + 0.004 * k), c + (yy - c) / (1.0 + 0.004 * k)
+        v = 128 + 38 * np.sin(2 * np.pi * x / 11 + 0.3) + 30 * np.sin(2 * np.pi * (x / 7.3 + y / 19)) + 24 * np.sin(2 * np.pi * y / 9 + 1.0) \
+            + 20 * np.sin(2 * np.pi * (x / 23 - y / 13))
+        ch = 128 + 50 * np.sin(2 * np.pi * (x / 29 + y / 37) + 0.7)
+        frames[k] = np.clip(np.rint(np.stack([v, 0.5 * v + 0.5 * ch, ch], axis=-1)), 0, 255).astype(np.uint8)
+    return frames
+
+
+def measure_part(name: str, frames: torch.Tensor, gop: int, search: int, subpels, deblocks, qps, parts, reps: int) -> list:
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    n, H, W, _ = frames.shape
+    y = hip.h264_planes(frames)[0]
+    p_pictures = n - len(range(0, n, gop))
+    rows = []
+    for qp in qps:
+        for subpel in subpels:
+            for deblock in deblocks:
+                for part in parts:
+                    enc = H264Encoder(qp, frames.device, gop=gop, search=search, subpel=subpel, deblock=deblock, part=part)
+                    ev, wall = timed(lambda: enc.encode(frames), reps)
+                    samples, recon = enc.encode(frames, return_recon=True)
+                    mse = float(((recon[0][:, :H, :W].to(torch.float64) - y[:, :H, :W].to(torch.float64)) ** 2).mean())
+                    row = dict(content=name, n=n, H=H, W=W, qp=qp, gop=gop, search=search, subpel=subpel, deblock=deblock, part=part,
+                               encode_ms_events=round(ev, 3), encode_ms_host_clock=round(wall, 3), frames_per_sec=round(n / wall * 1e3, 1),
+                               bytes_per_frame=int(sum(len(s) for s in samples) // n),
+                               y_psnr_db=round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None)
+                    ws = next(iter(enc._ws.values()))
+                    mv = ws["mv"]
+                    if part:
+                        split = (mv != mv[:, :, :, :1]).any(dim=-1).any(dim=-1)
+                        row["p8x8_share_of_p_macroblocks"] = round(float(split.sum()) / max(1, p_pictures * mv.shape[1] * mv.shape[2]), 4)
+                        ms = timed(lambda: hip.h264_motion_search_part(ws["y"], qp, gop, search, subpel, mv), reps)[0]
+                    elif subpel:
+                        ms = timed(lambda: hip.h264_motion_search_sub(ws["y"], qp, gop, search, subpel, mv), reps)[0]
+                    else:
+                        ms = timed(lambda: hip.h264_motion_search(ws["y"], qp, gop, search, mv), reps)[0]
+                    row.update(search_kernel_ms=round(ms, 3), search_share_of_encode=round(ms / ev, 3))
+                    print(json.dumps(row), flush=True)
+                    rows.append(row)
+                    del enc, recon, ws, mv
+                    torch.cuda.empty_cache()
+    return rows
+
+
+def main_part(args):
+    import h264_i4_ref as I4
+    import h264_me_ref as ME
+    import h264_part_ref as PT
+    from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
+    from stable_diffusion_videos_amd.upsampling import RealESRGANModel
+    dev = torch.device("cuda", 0)
+    result = dict(tool=f"tools/h264_bench.py --gop {args.gop} --search {args.search} --subpel {args.subpel} --deblock {args.deblock} --qp {args.qp} "
+                       f"--part {args.part}", gpu=torch.cuda.get_device_name(0), host=platform.processor() or platform.machine(), reps=args.reps, rows=[])
+    pipe = StableDiffusionWalkPipeline.from_pretrained("tiny").to(dev)
+    small = pipeline_frames(pipe, 128)
+    up = RealESRGANModel.from_pretrained("nateraw/real-esrgan")
+    up.to(dev)
+    big = torch.cat([up.upsample_u8(small[k:k + 2]) for k in range(0, 8, 2)])
+    del pipe, up
+    sets = [("tiny pipeline", lambda: small.contiguous()), ("tiny pipeline x4 upsampler", lambda: big.contiguous())]
+    for kind in ("fade", "pan2"):
+        sets.append((kind, lambda kind=kind: torch.from_numpy(ME.make_frames(kind, 48, 512, 512)).to(dev).contiguous()))
+    for kind in ("glyphs", "noise"):
+        sets.append((kind, lambda kind=kind: torch.from_numpy(I4.make_frames(kind, 48, 512, 512)).to(dev).contiguous()))
+    sets.append(("split", lambda: torch.from_numpy(PT.split_frames(8, 48, 512, 512)).to(dev).contiguous()))
+    sets.append(("zoom", lambda: torch.from_numpy(zoom_frames(48, 512)).to(dev).contiguous()))
+    for name, make in sets:
+        result["rows"] += measure_part(name, make(), args.gops[0], args.searches[0], args.subpels, args.deblocks, args.qps, args.parts, args.reps)
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    print(line)
+
+
 def main_deblock(args):
     import h264_i4_ref as I4
     import h264_me_ref as ME
@@ -416,7 +508,22 @@ def main():
     ap.add_argument("--intra4", default=None, help="I[,I...] (0, 1): one row per (gop, search, I); --gop and --search are then lists, 0 = Intra16x16 only")
     ap.add_argument("--deblock", default=None, help="D[,D...] (0, 1): one row per (qp, search, D) at one --gop N; 0 = the loop filter off")
     ap.add_argument("--qp", default=None, help="with --deblock: Q[,Q...] (0 .. 51), default 16")
+    ap.add_argument("--part", default=None, help="P[,P...] (0, 1): one row per (qp, subpel, deblock, P) at one --gop N > 1 and one --search R > 0")
     args = ap.parse_args()
+    if args.part is not None:
+        args.gops = [int(v) for v in args.gop.split(",")]
+        args.searches = [int(v) for v in (args.search or "0").split(",")]
+        args.subpel, args.deblock, args.qp = args.subpel or "0", args.deblock or "0", args.qp or "16"
+        args.subpels, args.deblocks = [int(v) for v in args.subpel.split(",")], [int(v) for v in args.deblock.split(",")]
+        args.qps, args.parts = [int(v) for v in args.qp.split(",")], [int(v) for v in args.part.split(",")]
+        if args.intra4 is not None or len(args.gops) != 1 or not 2 <= args.gops[0] <= 256 or len(args.searches) != 1 or args.searches[0] % 2 \
+                or not 2 <= args.searches[0] <= 16 or any(v not in (0, 1, 2, 4) for v in args.subpels) or any(v not in (0, 1) for v in args.deblocks + args.parts) \
+                or any(not 0 <= v <= 51 for v in args.qps):
+            raise SystemExit("--part takes 0 and 1, with one --gop N (2 .. 256), one --search R (even, 2 .. 16), --subpel S[,S...] (0, 1, 2, 4), "
+                             "--deblock D[,D...] (0, 1) and --qp Q[,Q...] (0 .. 51), without --intra4")
+        if not torch.cuda.is_available():
+            raise SystemExit("h264_bench needs the GPU (no fallback)")
+        return main_part(args)
     if args.qp is not None and args.deblock is None:
         raise SystemExit("--qp goes with --deblock (the other measurements are taken at qp 16)")
     if args.deblock is not None:
