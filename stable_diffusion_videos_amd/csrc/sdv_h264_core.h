@@ -1796,3 +1796,46 @@ inline void h264_part_lf_picture(uint8_t* ry, uint8_t* rcb, uint8_t* rcr, int mb
             }
         }
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Row slices (sdv_hip_h264_seg.h "H.264 row slices"): every macroblock row is cut into ``segs`` slices of nearly equal width, each an
+// independent bit stream with a wave of its own.  The pieces below are what the seg kernels, the host and the tests share: the number
+// of slices a row gets, a slice's first and last macroblock, its slot index and the scratch layout - that of the intra layout at
+// (n, mbh * segs, w'), so that sdv_h264_pack reads it unchanged.  Nothing above is touched.
+// ------------------------------------------------------------------------------------------------------------------------------------
+enum { kH264SegMax = 16 };                              // the largest row_slices setting
+enum { kH264SegSlotRows = 1024 };                       // sdv_h264_pack accepts at most this many slot rows a picture
+// slices actually written per row: the setting, at most one per macroblock, at most what sdv_h264_pack takes; the frame size alone decides
+H264_HD int h264_row_segments(int mbh, int mbw, int row_slices) {
+    int segs = row_slices < mbw ? row_slices : mbw;
+    if (segs > kH264SegSlotRows / mbh) segs = kH264SegSlotRows / mbh;
+    return segs < 1 ? 1 : segs;
+}
+// slice s of a row covers macroblocks h264_seg_first(s) .. h264_seg_first(s + 1) - 1: widths differ by at most one, none is empty (segs <= mbw)
+H264_HD int h264_seg_first(int s, int mbw, int segs) { return (int)((long long)s * mbw / segs); }
+H264_HD int h264_seg_width_max(int mbw, int segs) { return (mbw + segs - 1) / segs; }
+// the slot of a slice is that of an intra picture this many macroblocks wide: h264_gop_slot_mbw of the widest slice
+H264_HD int h264_seg_slot_mbw(int mbw, int segs) {
+    const int w = h264_seg_width_max(mbw, segs);
+    return w + 1 + w / 64;
+}
+H264_HD long long h264_seg_slot_index(long long f, int r, int s, int mbh, int segs) { return (f * mbh + r) * segs + s; }
+// what the entry points accept: 1 .. min(mbw, 16) slices a row and at most 1024 slot rows a picture
+H264_HD bool h264_seg_ok(int mbh, int mbw, int segs) {
+    return segs >= 1 && segs <= kH264SegMax && segs <= mbw && (long long)mbh * segs <= kH264SegSlotRows;
+}
+struct h264_seg_layout {
+    long long rows, slot, stride, starts_at, lens_at, bytes;
+};
+// the intra layout (sdv_hip.h "Capacity") at (n, mbh * segs, h264_seg_slot_mbw): slots at an 8-byte stride, an int64 start and an int32 length each
+H264_HD h264_seg_layout h264_seg_scratch_layout(int n, int mbh, int mbw, int segs) {
+    h264_seg_layout l;
+    l.rows = (long long)n * mbh * segs;
+    l.slot = 600LL * h264_seg_slot_mbw(mbw, segs) + 17;
+    l.stride = (l.slot + 7) & ~7LL;
+    l.starts_at = l.rows * l.stride;
+    l.lens_at = l.starts_at + 8 * l.rows;
+    l.bytes = l.lens_at + 4 * l.rows;
+    return l;
+}
+H264_HD long long h264_seg_out_bytes(int n, int mbh, int mbw, int segs) { return (long long)n * mbh * segs * (600LL * h264_seg_slot_mbw(mbw, segs) + 17); }

@@ -37,6 +37,12 @@ beside the 16x16 one and takes them where they are cheaper by more than their sy
 partition and the loop filter compares the vectors per partition.  tests/h264_part_ref.py restates and decodes it.  ``part`` 0, or ``part``
 1 without P pictures or without a search, is the code and the bytes of the other settings alone.
 
+``row_slices`` S in 1 .. 16 (opt-in, with every other setting, ``gop`` 1 included; include/sdv_hip_h264_seg.h and DESIGN.md "H.264 row
+slices") cuts every macroblock row into ``segs = max(1, min(S, mbw, 1024 // mbh))`` slices of nearly equal width, each an independent bit
+stream with a wave of its own: the GPU then has ``segs`` times as many chains to run side by side, at a few bytes per slice.  A slice start
+is a row start; vectors, the loop filter and the search do not stop there.  tests/h264_seg_ref.py restates and decodes it.  ``row_slices``
+1, or any S on a frame size with ``segs`` 1, is the code and the bytes of the other settings alone.
+
 Host side here: the workspaces, the copy back of the packed samples and their offsets.  Opt-in (video.py ``SDV_VIDEO_CODEC=h264-cavlc``).
 """
 from __future__ import annotations
@@ -54,6 +60,7 @@ DEFAULT_SUBPEL = 0                                                              
 DEFAULT_INTRA4 = 0                                                                              # a setting, not a measured optimum
 DEFAULT_DEBLOCK = 0                                                                             # a setting, not a measured optimum
 DEFAULT_PART = 0                                                                                # a setting, not a measured optimum
+DEFAULT_ROW_SLICES = 1                                                                          # a setting, not a measured optimum
 
 
 def check_qp(qp) -> int:
@@ -98,6 +105,12 @@ def check_part(part) -> int:
     return part
 
 
+def check_row_slices(row_slices) -> int:
+    if isinstance(row_slices, bool) or not isinstance(row_slices, int) or not 1 <= row_slices <= hip.H264_ROW_SLICES_MAX:
+        raise ValueError(f"h264 row_slices must be an integer in 1 .. {hip.H264_ROW_SLICES_MAX}, got {row_slices!r}")
+    return row_slices
+
+
 class H264Encoder:
     """``encode(frames_u8, first_index)``: uint8 ``[n, H, W, 3]`` tensor in GPU memory (H, W even) -> ``list[bytes]``, one mp4 sample
     (the picture's length-prefixed slice NAL units) per frame.  Picture k carries ``idr_pic_id = (first_index + k) & 1``.  With ``gop``
@@ -114,13 +127,20 @@ class H264Encoder:
     after each position but the last, whose filtered planes only ``return_recon`` reads (it then runs too); GOP workspaces at any ``gop``.
     ``part`` 1 (no effect unless ``gop`` > 1 and ``search`` > 0) runs the partition search, then every P position - and, without ``intra4``,
     the IDR position - through the four-vector entry points, and the four-vector filter with ``deblock``; the same number of launches.
+    ``row_slices`` S (1 .. 16, with every other setting) writes ``segs = max(1, min(S, mbw, 1024 // mbh))`` slices per macroblock row.
+    ``segs`` 1 (S = 1, a picture one macroblock wide, a very tall one) takes the route above and writes its bytes.  With ``segs`` > 1 every
+    setting combination runs the search (if any; the one-vector searches' result is expanded on the device to the four-vector layout
+    in quarter samples), then one seg launch per picture position (the Intra4x4 seg launch for the IDR position with ``intra4``), the
+    four-vector filter between positions with ``deblock``, and pack over ``mbh * segs`` slot rows; the single-launch
+    ``h264_encode_gops`` and ``h264_encode_rows`` routes are not used, so ``return_recon`` works at ``gop`` 1 too.
 
     Three entry points on the current stream (planes; rows; pack), then two copies into pinned memory: the n + 1 offsets, then the used
     prefix of the packed buffer - raw frames and planes stay in HBM.  Workspaces are cached per ``(n, H, W)`` and sized by the
     capacity bound of sdv_hip.h, so no batch can fail to fit."""
 
     def __init__(self, qp: int = DEFAULT_QP, device=None, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH,
-                 subpel: int = DEFAULT_SUBPEL, intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK, part: int = DEFAULT_PART):
+                 subpel: int = DEFAULT_SUBPEL, intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK, part: int = DEFAULT_PART,
+                 row_slices: int = DEFAULT_ROW_SLICES):
         self.qp = check_qp(qp)
         self.gop = check_gop(gop)
         self.search = check_search(search)
@@ -128,6 +148,7 @@ class H264Encoder:
         self.intra4 = check_intra4(intra4)
         self.deblock = check_deblock(deblock)
         self.part = check_part(part)
+        self.row_slices = check_row_slices(row_slices)
         self._parted = self.part == 1 and self.gop > 1 and self.search > 0                      # otherwise part 1 is today's route
         self.last_sync: List[int] = []
         self.device = torch.device(device) if device is not None else None
@@ -137,6 +158,11 @@ class H264Encoder:
     def _workspace(self, n: int, mbh: int, mbw: int, device) -> dict:
         key = (n, mbh, mbw, str(device))
         ws = self._ws.get(key)
+        if ws is None and hip.h264_row_segments(mbh, mbw, self.row_slices) > 1:
+            ws = self._seg_workspace(n, mbh, mbw, device)
+            if len(self._ws) >= 4:
+                self._ws.pop(next(iter(self._ws)))
+            self._ws[key] = ws
         if ws is None:
             gops = self.gop > 1 or self.intra4 == 1 or self.deblock == 1                     # Intra4x4 and the loop filter use the GOP slots at any gop
             cap = hip.h264_gop_out_bytes(n, mbh, mbw) if gops else hip.h264_out_bytes(n, mbh, mbw)
@@ -165,6 +191,28 @@ class H264Encoder:
             if len(self._ws) >= 4:                                                              # a walk uses one or two shapes
                 self._ws.pop(next(iter(self._ws)))
             self._ws[key] = ws
+        return ws
+
+    def _seg_workspace(self, n: int, mbh: int, mbw: int, device) -> dict:
+        """``row_slices``: slots of the seg layout, the reconstruction planes, the four-vector tensor of every route (zeros without a
+        search), the one-vector tensor a search without ``part`` writes, the side information with ``deblock``."""
+        segs = hip.h264_row_segments(mbh, mbw, self.row_slices)
+        cap = hip.h264_seg_out_bytes(n, mbh, mbw, segs)
+        ws = dict(segs=segs,
+                  y=torch.empty((n, 16 * mbh, 16 * mbw), dtype=torch.uint8, device=device),
+                  cb=torch.empty((n, 8 * mbh, 8 * mbw), dtype=torch.uint8, device=device),
+                  cr=torch.empty((n, 8 * mbh, 8 * mbw), dtype=torch.uint8, device=device),
+                  scratch=torch.empty((hip.h264_seg_scratch_bytes(n, mbh, mbw, segs),), dtype=torch.uint8, device=device),
+                  out=torch.empty((cap,), dtype=torch.uint8, device=device),
+                  offsets=torch.zeros((n + 1,), dtype=torch.int64, device=device),
+                  offsets_host=torch.empty((n + 1,), dtype=torch.int64, pin_memory=True),
+                  out_host=torch.empty((cap,), dtype=torch.uint8, pin_memory=True),
+                  mv=torch.zeros((n, mbh, mbw, 4, 2), dtype=torch.int16, device=device))
+        ws.update(ry=torch.empty_like(ws["y"]), rcb=torch.empty_like(ws["cb"]), rcr=torch.empty_like(ws["cr"]))
+        if self.search and self.gop > 1 and not self._parted:
+            ws.update(mv1=torch.zeros((n, mbh, mbw, 2), dtype=torch.int16, device=device))
+        if self.deblock:
+            ws.update(mbinfo=torch.zeros((n, mbh, mbw), dtype=torch.int32, device=device))
         return ws
 
     def _check_device(self, what: str, t):
@@ -203,7 +251,10 @@ class H264Encoder:
             return self._rows_and_pack(ws, n, mbh, mbw, first_index, return_recon)
 
     def _rows_and_pack(self, ws: dict, n: int, mbh: int, mbw: int, first_index: int, return_recon: bool = False):
-        if self._parted:
+        if ws.get("segs", 1) > 1:
+            self._seg_steps(ws, n, int(first_index), return_recon)
+            hip.h264_pack(ws["scratch"], n, mbh * ws["segs"], hip.h264_seg_slot_mbw(mbw, ws["segs"]), ws["out"], ws["offsets"])
+        elif self._parted:
             self._parted_steps(ws, n, int(first_index), return_recon)
             hip.h264_pack(ws["scratch"], n, mbh, hip.h264_gop_slot_mbw(mbw), ws["out"], ws["offsets"])
         elif self.deblock:
@@ -310,15 +361,49 @@ class H264Encoder:
                 hip.h264_deblock_part(*recon, self.qp, self.gop, k, ws["mbinfo"], ws["mv"])
 
 
+    def _seg_steps(self, ws: dict, n: int, first_index: int, filter_last: bool):
+        """``row_slices`` with more than one slice a row: the search of the settings (if any) over all P pictures, its one-vector result
+        written four times in quarter samples, then every picture position in order through the seg entry points (IDR pictures through
+        the Intra4x4 seg launch with ``intra4``, the k = 0 step without), and with ``deblock`` the four-vector filter between two
+        positions - it filters across slice boundaries as it does across rows.  Without a search the vectors are zeros and the step takes
+        its smallest range."""
+        planes, recon, segs = (ws["y"], ws["cb"], ws["cr"]), (ws["ry"], ws["rcb"], ws["rcr"]), ws["segs"]
+        last = min(self.gop, n)
+        searched = bool(self.search) and self.gop > 1
+        search, sub = (self.search, self.subpel) if searched else (2, 0)
+        if last > 1 and self._parted:
+            hip.h264_motion_search_part(ws["y"], self.qp, self.gop, self.search, self.subpel, ws["mv"])
+        elif last > 1 and searched:
+            if sub:
+                hip.h264_motion_search_sub(ws["y"], self.qp, self.gop, self.search, sub, ws["mv1"])
+                ws["mv"].copy_(ws["mv1"][:, :, :, None, :].expand(-1, -1, -1, 4, -1))             # quarter samples already
+            else:
+                hip.h264_motion_search(ws["y"], self.qp, self.gop, self.search, ws["mv1"])
+                ws["mv"].copy_((ws["mv1"] * 4)[:, :, :, None, :].expand(-1, -1, -1, 4, -1))       # whole samples -> quarter samples
+        for k in range(last):
+            if k == 0 and self.intra4 and self.deblock:
+                hip.h264_encode_idr4_seg_lf(*planes, self.qp, self.gop, first_index, *recon, ws["scratch"], ws["mbinfo"], segs)
+            elif k == 0 and self.intra4:
+                hip.h264_encode_idr4_seg(*planes, self.qp, self.gop, first_index, *recon, ws["scratch"], segs)
+            elif self.deblock:
+                hip.h264_encode_gop_step_seg_lf(*planes, self.qp, self.gop, k, search, sub, first_index, ws["mv"], *recon, ws["scratch"],
+                                                ws["mbinfo"], segs)
+            else:
+                hip.h264_encode_gop_step_seg(*planes, self.qp, self.gop, k, search, sub, first_index, ws["mv"], *recon, ws["scratch"], segs)
+            if self.deblock and (k + 1 < last or filter_last):
+                hip.h264_deblock_part(*recon, self.qp, self.gop, k, ws["mbinfo"], ws["mv"])
+
+
 _encoders: Dict[tuple, H264Encoder] = {}
 
 
 def encoder_for(qp: int, device, gop: int = DEFAULT_GOP, search: int = DEFAULT_SEARCH, subpel: int = DEFAULT_SUBPEL,
-                intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK, part: int = DEFAULT_PART) -> H264Encoder:
+                intra4: int = DEFAULT_INTRA4, deblock: int = DEFAULT_DEBLOCK, part: int = DEFAULT_PART,
+                row_slices: int = DEFAULT_ROW_SLICES) -> H264Encoder:
     """One cached encoder (and its workspaces) per quality setting, GOP length, search range, vector grid, intra setting, loop filter
-    setting, partition setting and device."""
+    setting, partition setting, row slice setting and device."""
     key = (check_qp(qp), str(device), check_gop(gop), check_search(search), check_subpel(subpel), check_intra4(intra4), check_deblock(deblock),
-           check_part(part))
+           check_part(part), check_row_slices(row_slices))
     if key not in _encoders:
-        _encoders[key] = H264Encoder(qp, device, gop, search, subpel, intra4, deblock, part)
+        _encoders[key] = H264Encoder(qp, device, gop, search, subpel, intra4, deblock, part, row_slices)
     return _encoders[key]

@@ -145,6 +145,18 @@ _H264_PART_SIGNATURES = {
     "sdv_h264_deblock_part": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
 }
 H264_PART_SYMBOLS = tuple(_H264_PART_SIGNATURES)
+# include/sdv_hip_h264_seg.h: several slices per macroblock row: the four-vector per-position pair and the Intra4x4 pair, each with ``segs``
+# before the stream
+_H264_SEG_SIGNATURES = {
+    "sdv_h264_encode_gop_step_seg": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 +
+                                     [C.c_int64, C.c_int32, C.c_void_p]),
+    "sdv_h264_encode_gop_step_seg_lf": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 +
+                                        [C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "sdv_h264_encode_idr4_seg": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "sdv_h264_encode_idr4_seg_lf": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4 +
+                                    [C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+}
+H264_SEG_SYMBOLS = tuple(_H264_SEG_SIGNATURES)
 
 
 def lib_path() -> Path:
@@ -166,7 +178,7 @@ def load(build_if_missing: bool = False):
                 "(there is no CPU / eager fallback for the hot path)")
     lib = C.CDLL(str(_LIB_PATH))
     for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_H264_SUB_SIGNATURES, **_H264_I4_SIGNATURES, **_H264_LF_SIGNATURES,
-                              **_H264_PART_SIGNATURES}.items():
+                              **_H264_PART_SIGNATURES, **_H264_SEG_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -2111,6 +2123,148 @@ def h264_deblock_part(ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, qp
     """``h264_deblock`` with four vectors per macroblock (``mv`` int16 ``[n, mbh, mbw, 4, 2]``, always quarter samples) and the side
     information of ``h264_encode_gop_step_part_lf`` (``torch.ops.sdv.k_h264_deblock_part`` -> sdv_h264_deblock_part)."""
     _k_h264_deblock_part(ry, rcb, rcr, int(qp), int(gop), int(k), mbinfo, mv, int(waves))
+
+
+# ---- row slices (include/sdv_hip_h264_seg.h): up to 16 slices per macroblock row, one wave each ----
+H264_ROW_SLICES_MAX = 16
+H264_SEG_SLOT_ROWS = 1024
+
+
+def h264_row_segments(mbh: int, mbw: int, row_slices: int) -> int:
+    """The slices written per macroblock row with the setting ``row_slices``: ``max(1, min(row_slices, mbw, 1024 // mbh))`` - at most one
+    per macroblock, and at most the 1024 slot rows a picture that sdv_h264_pack accepts.  The frame size alone decides."""
+    return max(1, min(int(row_slices), int(mbw), H264_SEG_SLOT_ROWS // int(mbh)))
+
+
+def h264_seg_slot_mbw(mbw: int, segs: int) -> int:
+    """A slice of at most ``ceil(mbw / segs)`` macroblocks lies in the slot of an intra picture this many macroblocks wide."""
+    return h264_gop_slot_mbw((int(mbw) + int(segs) - 1) // int(segs))
+
+
+def h264_seg_scratch_bytes(n: int, mbh: int, mbw: int, segs: int) -> int:
+    """The intra layout at ``(n, mbh * segs, h264_seg_slot_mbw(mbw, segs))``."""
+    return h264_scratch_bytes(n, int(mbh) * int(segs), h264_seg_slot_mbw(mbw, segs))
+
+
+def h264_seg_out_bytes(n: int, mbh: int, mbw: int, segs: int) -> int:
+    """The capacity sdv_h264_pack demands of ``out`` behind the seg entry points."""
+    return h264_out_bytes(n, int(mbh) * int(segs), h264_seg_slot_mbw(mbw, segs))
+
+
+def _h264_seg_common(what, y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, mbinfo, segs):
+    n, mbh, mbw = _h264_plane_grid(what, y, cb, cr)
+    if mbinfo is not None:
+        _h264_mbinfo_check(what, mbinfo, n, mbh, mbw)
+    if not 0 <= qp <= 51:
+        raise SdvHipError(f"{what}: qp must be 0 .. 51, got {qp}")
+    if not 1 <= gop <= H264_GOP_MAX:
+        raise SdvHipError(f"{what}: gop must be 1 .. {H264_GOP_MAX}, got {gop}")
+    if mbw > H264_GOP_MAX_MBW:
+        raise SdvHipError(f"{what}: pictures wider than {H264_GOP_MAX_MBW} macroblocks are not coded in the GOP path's slots, got mbw={mbw}")
+    if not 1 <= segs <= min(mbw, H264_ROW_SLICES_MAX):
+        raise SdvHipError(f"{what}: segs must be 1 .. min(mbw, {H264_ROW_SLICES_MAX}) = {min(mbw, H264_ROW_SLICES_MAX)}, got {segs}")
+    if mbh * segs > H264_SEG_SLOT_ROWS:
+        raise SdvHipError(f"{what}: mbh * segs = {mbh * segs} is above the {H264_SEG_SLOT_ROWS} slot rows a picture may have")
+    if first_index < 0:
+        raise SdvHipError(f"{what}: first_index must be >= 0, got {first_index}")
+    _h264_u8(what, "ry", ry, y.shape)
+    _h264_u8(what, "rcb", rcb, cb.shape)
+    _h264_u8(what, "rcr", rcr, cr.shape)
+    _h264_u8(what, "scratch", scratch)
+    need = h264_seg_scratch_bytes(n, mbh, mbw, segs)
+    if scratch.ndim != 1 or scratch.numel() < need:
+        raise SdvHipError(f"{what}: scratch holds {scratch.numel()} bytes, {n * mbh * segs} slices of at most {(mbw + segs - 1) // segs} "
+                          f"macroblocks need {need}")
+    return n, mbh, mbw
+
+
+def _h264_encode_gop_step_seg_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch, segs, mbinfo=None):
+    what = "h264_encode_gop_step_seg" if mbinfo is None else "h264_encode_gop_step_seg_lf"
+    n, mbh, mbw = _h264_seg_common(what, y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, mbinfo, segs)
+    if not 0 <= k < min(gop, n):
+        raise SdvHipError(f"{what}: position k must be 0 .. min(gop, n) - 1 = {min(gop, n) - 1}, got {k}")
+    _h264_search_range(what, search)
+    _h264_part_subpel_value(what, subpel)
+    _h264_part_mv_check(what, mv, n, mbh, mbw)
+    lib = load()
+    args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(k), int(search), int(subpel),
+            int(first_index) & 0x7fffffff, _ptr(mv, name="mv"), mv.numel(), _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"),
+            _ptr(scratch, name="scratch"), scratch.numel())
+    if mbinfo is not None:
+        lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+        _launch("h264_encode_gop_step_seg_lf", dict(bytes=3.0 * y.numel() / min(gop, n)),
+                lambda: _check(lib.sdv_h264_encode_gop_step_seg_lf(*args, *lf, int(segs), _stream()), "sdv_h264_encode_gop_step_seg_lf"))
+        return
+    _launch("h264_encode_gop_step_seg", dict(bytes=3.0 * y.numel() / min(gop, n)),
+            lambda: _check(lib.sdv_h264_encode_gop_step_seg(*args, int(segs), _stream()), "sdv_h264_encode_gop_step_seg"))
+
+
+def _h264_encode_gop_step_seg_lf_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch, mbinfo, segs):
+    _h264_encode_gop_step_seg_impl(y, cb, cr, qp, gop, k, search, subpel, first_index, mv, ry, rcb, rcr, scratch, segs,
+                                   _h264_mbinfo_given("h264_encode_gop_step_seg_lf", mbinfo))
+
+
+def _h264_encode_idr4_seg_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, segs, mbinfo=None):
+    what = "h264_encode_idr4_seg" if mbinfo is None else "h264_encode_idr4_seg_lf"
+    n, mbh, mbw = _h264_seg_common(what, y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, mbinfo, segs)
+    lib = load()
+    args = (_ptr(y, name="y"), _ptr(cb, name="cb"), _ptr(cr, name="cr"), n, mbh, mbw, int(qp), int(gop), int(first_index) & 0x7fffffff,
+            _ptr(ry, name="ry"), _ptr(rcb, name="rcb"), _ptr(rcr, name="rcr"), _ptr(scratch, name="scratch"), scratch.numel())
+    if mbinfo is not None:
+        lf = _h264_mbinfo_args(what, mbinfo, n, mbh, mbw)
+        _launch("h264_encode_idr4_seg_lf", dict(bytes=3.0 * y.numel() / gop),
+                lambda: _check(lib.sdv_h264_encode_idr4_seg_lf(*args, *lf, int(segs), _stream()), "sdv_h264_encode_idr4_seg_lf"))
+        return
+    _launch("h264_encode_idr4_seg", dict(bytes=3.0 * y.numel() / gop),
+            lambda: _check(lib.sdv_h264_encode_idr4_seg(*args, int(segs), _stream()), "sdv_h264_encode_idr4_seg"))
+
+
+def _h264_encode_idr4_seg_lf_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, mbinfo, segs):
+    _h264_encode_idr4_seg_impl(y, cb, cr, qp, gop, first_index, ry, rcb, rcr, scratch, segs, _h264_mbinfo_given("h264_encode_idr4_seg_lf", mbinfo))
+
+
+_k_h264_encode_gop_step_seg = _defop("k_h264_encode_gop_step_seg(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int k, int search, int subpel, "
+                                     "int first_index, Tensor mv, Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch, int segs) -> ()",
+                                     _h264_encode_gop_step_seg_impl)
+_k_h264_encode_gop_step_seg_lf = _defop("k_h264_encode_gop_step_seg_lf(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int k, int search, int subpel, "
+                                        "int first_index, Tensor mv, Tensor(a!) ry, Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch, "
+                                        "Tensor(e!) mbinfo, int segs) -> ()", _h264_encode_gop_step_seg_lf_impl)
+_k_h264_encode_idr4_seg = _defop("k_h264_encode_idr4_seg(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int first_index, Tensor(a!) ry, "
+                                 "Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch, int segs) -> ()", _h264_encode_idr4_seg_impl)
+_k_h264_encode_idr4_seg_lf = _defop("k_h264_encode_idr4_seg_lf(Tensor y, Tensor cb, Tensor cr, int qp, int gop, int first_index, Tensor(a!) ry, "
+                                    "Tensor(b!) rcb, Tensor(c!) rcr, Tensor(d!) scratch, Tensor(e!) mbinfo, int segs) -> ()",
+                                    _h264_encode_idr4_seg_lf_impl)
+
+
+def h264_encode_gop_step_seg(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, k: int, search: int, subpel: int,
+                             first_index: int, mv: torch.Tensor, ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor,
+                             segs: int):
+    """``h264_encode_gop_step_part`` with ``segs`` slices per macroblock row, one wave each (rule of sdv_hip_h264_seg.h;
+    ``torch.ops.sdv.k_h264_encode_gop_step_seg`` -> sdv_h264_encode_gop_step_seg).  ``scratch`` holds ``h264_seg_scratch_bytes``; pack with
+    ``h264_pack(scratch, n, mbh * segs, h264_seg_slot_mbw(mbw, segs), ...)``.  ``segs`` 1 writes ``h264_encode_gop_step_part``'s bytes."""
+    _k_h264_encode_gop_step_seg(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch, int(segs))
+
+
+def h264_encode_gop_step_seg_lf(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, k: int, search: int, subpel: int,
+                                first_index: int, mv: torch.Tensor, ry: torch.Tensor, rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor,
+                                mbinfo: torch.Tensor, segs: int):
+    """``h264_encode_gop_step_seg`` for a stream with the loop filter on (``torch.ops.sdv.k_h264_encode_gop_step_seg_lf`` ->
+    sdv_h264_encode_gop_step_seg_lf): ``mbinfo`` takes the side information words; ``h264_deblock_part`` for the same ``k`` follows."""
+    _k_h264_encode_gop_step_seg_lf(y, cb, cr, int(qp), int(gop), int(k), int(search), int(subpel), int(first_index), mv, ry, rcb, rcr, scratch,
+                                   mbinfo, int(segs))
+
+
+def h264_encode_idr4_seg(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, first_index: int, ry: torch.Tensor,
+                         rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor, segs: int):
+    """``h264_encode_idr4`` with ``segs`` slices per macroblock row (``torch.ops.sdv.k_h264_encode_idr4_seg`` -> sdv_h264_encode_idr4_seg)."""
+    _k_h264_encode_idr4_seg(y, cb, cr, int(qp), int(gop), int(first_index), ry, rcb, rcr, scratch, int(segs))
+
+
+def h264_encode_idr4_seg_lf(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, qp: int, gop: int, first_index: int, ry: torch.Tensor,
+                            rcb: torch.Tensor, rcr: torch.Tensor, scratch: torch.Tensor, mbinfo: torch.Tensor, segs: int):
+    """``h264_encode_idr4_seg`` with the side information of the loop filter (``torch.ops.sdv.k_h264_encode_idr4_seg_lf`` ->
+    sdv_h264_encode_idr4_seg_lf)."""
+    _k_h264_encode_idr4_seg_lf(y, cb, cr, int(qp), int(gop), int(first_index), ry, rcb, rcr, scratch, mbinfo, int(segs))
 
 
 def _h264_pack_impl(scratch, n, mbh, mbw, out, offsets):

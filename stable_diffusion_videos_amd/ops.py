@@ -4,7 +4,7 @@ HIP kernels through PyTorch-ROCm custom ops"; SURVEY.md 8b proposes exactly this
 
 Two layers, both in the ``sdv`` namespace:
 
-* ``torch.ops.sdv.k_*`` (registered in ``hip.py``, 51 ops - the H.264 encoder's ``k_h264_planes`` / ``k_h264_encode_rows`` / ``k_h264_encode_gops`` / ``k_h264_motion_search`` / ``k_h264_encode_gop_step`` / ``k_h264_motion_search_sub`` / ``k_h264_encode_gop_step_sub`` / ``k_h264_encode_idr4`` / ``k_h264_encode_gop_step_lf`` / ``k_h264_encode_gop_step_sub_lf`` / ``k_h264_encode_idr4_lf`` / ``k_h264_deblock`` / ``k_h264_motion_search_part`` / ``k_h264_encode_gop_step_part`` / ``k_h264_encode_gop_step_part_lf`` / ``k_h264_deblock_part`` / ``k_h264_pack`` among them): ONE op per kernel launch of the C ABI (include/sdv_hip.h, include/sdv_hip_ext.h, include/sdv_hip_h264_sub.h, include/sdv_hip_h264_i4.h, include/sdv_hip_h264_lf.h) - schema with
+* ``torch.ops.sdv.k_*`` (registered in ``hip.py``, 55 ops - the H.264 encoder's ``k_h264_planes`` / ``k_h264_encode_rows`` / ``k_h264_encode_gops`` / ``k_h264_motion_search`` / ``k_h264_encode_gop_step`` / ``k_h264_motion_search_sub`` / ``k_h264_encode_gop_step_sub`` / ``k_h264_encode_idr4`` / ``k_h264_encode_gop_step_lf`` / ``k_h264_encode_gop_step_sub_lf`` / ``k_h264_encode_idr4_lf`` / ``k_h264_deblock`` / ``k_h264_motion_search_part`` / ``k_h264_encode_gop_step_part`` / ``k_h264_encode_gop_step_part_lf`` / ``k_h264_deblock_part`` / ``k_h264_encode_gop_step_seg`` / ``k_h264_encode_gop_step_seg_lf`` / ``k_h264_encode_idr4_seg`` / ``k_h264_encode_idr4_seg_lf`` / ``k_h264_pack`` among them): ONE op per kernel launch of the C ABI (include/sdv_hip.h, include/sdv_hip_ext.h, include/sdv_hip_h264_sub.h, include/sdv_hip_h264_i4.h, include/sdv_hip_h264_lf.h) - schema with
   the mutated outputs annotated, an implementation that passes ``data_ptr()`` + the current HIP stream to libsdv_hip.so, a
   Meta kernel.  **The product runs on these**: every wrapper in ``hip.py`` that ``engine.py`` / ``pipeline.py`` / ``text.py`` /
   ``esrgan.py`` call packs its arguments and calls the op (``tests/test_host.py::test_every_launch_is_a_torch_custom_op`` checks

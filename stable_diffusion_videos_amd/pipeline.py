@@ -126,6 +126,7 @@ class StableDiffusionWalkPipeline:
         self.h264_subpel = 0               # grid of those vectors: 0 = even whole samples, 1 = whole, 2 = half, 4 = quarter samples; SDV_H264_SUBPEL wins
         self.h264_intra4 = 0               # 1 = its IDR pictures use Intra4x4 prediction (I_NxN against Intra16x16 per macroblock); SDV_H264_INTRA4 wins
         self.h264_part = 0                 # 1 = its inter macroblocks may carry one vector per 8x8 quadrant (P_8x8; needs gop > 1 and search > 0); SDV_H264_PART wins
+        self.h264_row_slices = 1           # slices per macroblock row of that track, 1 .. 16 (one wave each on the GPU; any other setting); SDV_H264_ROW_SLICES wins
         self.h264_deblock = 0              # 1 = its in-loop deblocking filter is on (P pictures predict from filtered pictures); SDV_H264_DEBLOCK wins
         self.noise_device = "cpu"          # portable seeds
         self.embed_interp = "lerp"         # reference torch path lerps embeddings (:467); "slerp" = flax behaviour
@@ -737,6 +738,20 @@ class StableDiffusionWalkPipeline:
             raise ValueError(f"SDV_H264_PART / h264_part must be 0 or 1, got {part!r}")
         return part
 
+    def h264_row_slices_choice(self) -> int:
+        """Into how many slices the ``h264-cavlc`` video track cuts every macroblock row: the environment variable SDV_H264_ROW_SLICES
+        (1 .. 16) when it is set, else ``self.h264_row_slices``.  1 = one slice per row; a setting, not a measured optimum."""
+        env = os.environ.get("SDV_H264_ROW_SLICES")
+        if not env:
+            row_slices = self.h264_row_slices
+        elif env.isdigit() and 1 <= int(env) <= 16:
+            row_slices = int(env)
+        else:
+            raise ValueError(f"SDV_H264_ROW_SLICES must be an integer in 1 .. 16, got {env!r}")
+        if isinstance(row_slices, bool) or not isinstance(row_slices, int) or not 1 <= row_slices <= 16:
+            raise ValueError(f"SDV_H264_ROW_SLICES / h264_row_slices must be an integer in 1 .. 16, got {row_slices!r}")
+        return row_slices
+
     def h264_deblock_choice(self) -> int:
         """Whether the ``h264-cavlc`` video track runs the in-loop deblocking filter: the environment variable SDV_H264_DEBLOCK (0 or 1)
         when it is set, else ``self.h264_deblock``.  0 = every slice switches the filter off; a setting, not a measured optimum."""
@@ -985,7 +1000,7 @@ class StableDiffusionWalkPipeline:
                                 h264_qp=self.h264_qp_choice(), h264_gop=self.h264_gop_choice(),
                                 h264_search=self.h264_search_choice(), h264_subpel=self.h264_subpel_choice(),
                                 h264_intra4=self.h264_intra4_choice(), h264_deblock=self.h264_deblock_choice(),
-                                h264_part=self.h264_part_choice())  # :787-796
+                                h264_part=self.h264_part_choice(), h264_row_slices=self.h264_row_slices_choice())  # :787-796
             result = make_video_pyav(save_path_root, audio_filepath=audio_filepath, fps=fps, audio_offset=audio_start_sec,
                                      audio_duration=sum(num_interpolation_steps) / fps, output_filepath=output_filepath,
                                      glob_pattern=f"**/*{image_file_ext}", sr=44100, codec=self.video_codec,
@@ -993,7 +1008,8 @@ class StableDiffusionWalkPipeline:
                                      h264_search=self.h264_search_choice(),
                                      h264_subpel=self.h264_subpel_choice(),
                                      h264_intra4=self.h264_intra4_choice(),
-                                     h264_deblock=self.h264_deblock_choice(), h264_part=self.h264_part_choice())                # :798-807
+                                     h264_deblock=self.h264_deblock_choice(), h264_part=self.h264_part_choice(),
+                                     h264_row_slices=self.h264_row_slices_choice())         # :798-807
         if world_size > 1:
             parallel.barrier()
             result = str(output_filepath) if result is None else result

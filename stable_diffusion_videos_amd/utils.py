@@ -130,11 +130,11 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
                     audio_offset: int = 0, audio_duration: int = 2, sr: int = 22050,
                     output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png", codec=None, h264_qp=None,
                     h264_gop=None, h264_search=None, h264_subpel=None, h264_intra4=None, h264_deblock=None,
-                    h264_part=None):
+                    h264_part=None, h264_row_slices=None):
     """mp4 muxing (utils.py:69-128).  Needs torchvision/pyav + ffmpeg, which this image lacks; the frames
     on disk are the product of the hot path, so ``walk(make_video=False)`` is fully functional without it."""
     from .video import make_video_pyav as _impl
     return _impl(frames_or_frame_dir, audio_filepath=audio_filepath, fps=fps, audio_offset=audio_offset,
                  audio_duration=audio_duration, sr=sr, output_filepath=output_filepath, glob_pattern=glob_pattern, codec=codec,
                  h264_qp=h264_qp, h264_gop=h264_gop, h264_search=h264_search, h264_subpel=h264_subpel, h264_intra4=h264_intra4,
-                 h264_deblock=h264_deblock, h264_part=h264_part)
+                 h264_deblock=h264_deblock, h264_part=h264_part, h264_row_slices=h264_row_slices)

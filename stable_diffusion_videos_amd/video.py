@@ -21,7 +21,9 @@ names the range (``"h264 (CAVLC, gop N, search R)"``, ``LAST_CODEC["search"]``);
 with Intra4x4 prediction (``" + intra4"`` behind the name, ``LAST_CODEC["intra4"]``); ``h264_deblock`` 1 (``pipe.h264_deblock``,
 ``SDV_H264_DEBLOCK``; with every other setting) switches the in-loop deblocking filter on (``" + deblock"`` behind the name,
 ``LAST_CODEC["deblock"]``); ``h264_part`` 1 (``pipe.h264_part``, ``SDV_H264_PART``; no effect unless ``h264_gop`` > 1 and ``h264_search``
-> 0) gives inter macroblocks one vector per 8x8 quadrant, ``P_8x8`` (``" + part"`` behind the name, ``LAST_CODEC["part"]``).
+> 0) gives inter macroblocks one vector per 8x8 quadrant, ``P_8x8`` (``" + part"`` behind the name, ``LAST_CODEC["part"]``);
+``h264_row_slices`` S in 1 .. 16 (``pipe.h264_row_slices``, ``SDV_H264_ROW_SLICES``; with every other setting) cuts every macroblock row
+into up to S slices, one wave each on the GPU (``" + S row slices"`` behind the name, ``LAST_CODEC["row_slices"]``).
 Frames are read once each (the reference's pairwise ``torch.cat``
 is O(n^2), :91-93).
 """
@@ -235,7 +237,7 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
                     output_filepath: Union[str, Path] = "output.mp4", glob_pattern: str = "*.png", codec: Optional[str] = None,
                     h264_qp: Optional[int] = None, h264_gop: Optional[int] = None, h264_search: Optional[int] = None,
                     h264_subpel: Optional[int] = None, h264_intra4: Optional[int] = None, h264_deblock: Optional[int] = None,
-                    h264_part: Optional[int] = None):
+                    h264_part: Optional[int] = None, h264_row_slices: Optional[int] = None):
     """Write the frames (a directory of images or a (T,C,H,W) uint8 tensor) to ``output_filepath`` and return it.  ``codec``: what
     ``SDV_VIDEO_CODEC`` selects (the variable wins): ``"h264"`` (I_PCM), ``"mjpeg"`` or ``"h264-cavlc"`` - the entropy-coded intra
     stream of h264_cavlc.py at quantiser ``h264_qp`` (0 .. 51, default 16), compressed in GPU memory; ``h264_gop``
@@ -246,7 +248,8 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     ``h264_intra4`` (0 or 1, default 0) 1 codes the IDR pictures with Intra4x4 prediction (``I_NxN`` against Intra16x16 per macroblock);
     ``h264_deblock`` (0 or 1, default 0) 1 switches the in-loop deblocking filter on (P pictures then predict from filtered pictures);
     ``h264_part`` (0 or 1, default 0) 1 lets inter macroblocks carry one vector per 8x8 quadrant (``P_8x8``; no effect unless ``h264_gop`` >
-    1 and ``h264_search`` > 0)."""
+    1 and ``h264_search`` > 0); ``h264_row_slices`` (1 .. 16, default 1) S > 1 cuts every macroblock row into up to S slices of nearly equal
+    width (``max(1, min(S, mbw, 1024 // mbh))`` of them), each an independent bit stream with a wave of its own."""
     output_filepath = str(output_filepath)
     gpu_frames = None                      # a uint8 tensor in GPU memory: a Motion-JPEG track is compressed there (jpeg.py)
     if isinstance(frames_or_frame_dir, torch.Tensor) and frames_or_frame_dir.is_cuda and frames_or_frame_dir.dtype == torch.uint8 \
@@ -298,6 +301,8 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
         deblock = check_deblock(DEFAULT_DEBLOCK if h264_deblock is None else h264_deblock)
         from .h264_cavlc import DEFAULT_PART, check_part
         part = check_part(DEFAULT_PART if h264_part is None else h264_part)
+        from .h264_cavlc import DEFAULT_ROW_SLICES, check_row_slices
+        row_slices = check_row_slices(DEFAULT_ROW_SLICES if h264_row_slices is None else h264_row_slices)
         if h % 2 or w % 2:
             codec = "h264"                                                                     # (the odd-size rule below sends it to Motion-JPEG)
         elif gpu_frames is not None:
@@ -346,10 +351,14 @@ def make_video_pyav(frames_or_frame_dir: Union[str, Path, torch.Tensor] = "./ima
     if codec == "h264-cavlc" and part and gop > 1 and search > 0:
         LAST_CODEC["video"] += " + part"
         LAST_CODEC["part"] = part
+    if codec == "h264-cavlc" and row_slices > 1:
+        LAST_CODEC["video"] += f" + {row_slices} row slices"
+        LAST_CODEC["row_slices"] = row_slices
     if codec == "h264-cavlc":
         from .h264_cavlc import encoder_for as h264_encoder_for
         active = gop > 1 and search > 0                                                    # subpel takes effect only on searched P pictures
-        enc = h264_encoder_for(qp, cavlc_device, gop, search if gop > 1 else 0, subpel if active else 0, intra4, deblock, part if active else 0)
+        enc = h264_encoder_for(qp, cavlc_device, gop, search if gop > 1 else 0, subpel if active else 0, intra4, deblock, part if active else 0,
+                               row_slices)
         step = max(1, H264_BATCH_BYTES // (h * w * 3))                                      # batches of about 64 MB of raw frames
         step = max(gop, step // gop * gop)                                                  # whole GOPs: the file does not depend on it
         sync: Optional[List[int]] = [] if gop > 1 else None

@@ -4,6 +4,7 @@
     python tools/h264_bench.py [--out FILE] [--reps 5] --gop N[,N...] --search R[,R...] --intra4 0,1
     python tools/h264_bench.py [--out FILE] [--reps 5] --gop N --search R[,R...] --qp Q[,Q...] --deblock 0,1
     python tools/h264_bench.py [--out FILE] [--reps 5] --gop N --search R --subpel S[,S...] --deblock D[,D...] --qp Q[,Q...] --part 0,1
+    python tools/h264_bench.py [--out FILE] [--reps 5] --gop N --search R[,R...] --subpel S[,S...] --deblock D[,D...] --part P[,P...] --qp Q[,Q...] --row-slices 1,2,4,8
 
 Cases: 128 frames of 512 x 512 and 8 frames of 2048 x 2048, each with two contents: what the tiny pipeline decodes (seeded synthetic
 weights; the 2048 x 2048 frames are its 512 x 512 frames through the x4 upsampler, as ``walk(upsample=True)`` makes them) and uniform
@@ -49,6 +50,14 @@ launch alone, and for P = 1 the share of the P pictures' macroblocks for which t
 P_8x8 candidates; the mode decision may still code one of them intra).  Two more synthetic kinds have motion that differs inside a
 macroblock: ``split`` (the upper 8 rows of every macroblock row glide right by 2 samples a picture, the lower 8 left) and ``zoom`` (the
 same texture magnified by 0.4 % a picture about the centre).  The P = 0 rows of a run are the comparison.
+
+With ``--row-slices S[,S...]`` (each S 1 .. 16; one ``--gop`` N, and ``--search``, ``--subpel``, ``--deblock``, ``--part`` and ``--qp`` lists,
+defaults 0, 0, 0, 0 and 16) the tool measures several slices per macroblock row (h264_cavlc.H264Encoder(..., row_slices=S)) on the tiny
+pipeline's frames (128 x 512 x 512, and 8 x 2048 x 2048 through the x4 upsampler): one row per (Q, R, S', D, P, S) - combinations in
+which a setting has no effect (subpel or part without a search) are left out - with encode() ms (HIP events, the copy back included;
+median and the spread of the repetitions), frames/s, bytes per frame, Y-PSNR of the reconstruction and the number of chains
+(GOPs x macroblock rows x slices a row) of a per-position launch.  The S values alternate in the innermost loop.  The S = 1 rows are the
+comparison: they run the code of the other settings alone.
 
 There is no fallback: without a GPU this tool fails.
 """
@@ -402,6 +411,80 @@ def main_part(args):
     print(line)
 
 
+def timed_spread(fn, reps: int):
+    """``timed`` that keeps the repetitions: (median, minimum, maximum HIP-event ms, median host-clock ms) of fn() after two warm-up calls."""
+    fn(), fn()
+    gpu_ms, wall_ms = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        wall_ms.append((time.perf_counter() - t0) * 1e3)
+        gpu_ms.append(e0.elapsed_time(e1))
+    return float(np.median(gpu_ms)), float(min(gpu_ms)), float(max(gpu_ms)), float(np.median(wall_ms))
+
+
+def measure_seg(name: str, frames: torch.Tensor, gop: int, searches, subpels, deblocks, parts, qps, row_slices, reps: int) -> list:
+    from stable_diffusion_videos_amd import hip
+    from stable_diffusion_videos_amd.h264_cavlc import H264Encoder
+    n, H, W, _ = frames.shape
+    mbh, mbw = hip.h264_mb_grid(H, W)
+    y = hip.h264_planes(frames)[0]
+    rows = []
+    for qp in qps:
+        for search in searches:
+            for subpel in subpels:
+                for deblock in deblocks:
+                    for part in parts:
+                        if (subpel or part) and not (search and gop > 1):                   # no effect: the row would repeat another
+                            continue
+                        for s in row_slices:
+                            enc = H264Encoder(qp, frames.device, gop=gop, search=search, subpel=subpel, deblock=deblock, part=part, row_slices=s)
+                            ev, lo, hi, wall = timed_spread(lambda: enc.encode(frames), reps)
+                            samples, recon = enc.encode(frames, return_recon=True)
+                            mse = float(((recon[0][:, :H, :W].to(torch.float64) - y[:, :H, :W].to(torch.float64)) ** 2).mean())
+                            segs = hip.h264_row_segments(mbh, mbw, s)
+                            row = dict(content=name, n=n, H=H, W=W, qp=qp, gop=gop, search=search, subpel=subpel, deblock=deblock, part=part, row_slices=s,
+                                       segs=segs, chains=-(-n // gop) * mbh * segs, encode_ms_events=round(ev, 3), encode_ms_events_min=round(lo, 3),
+                                       encode_ms_events_max=round(hi, 3), encode_ms_host_clock=round(wall, 3), frames_per_sec=round(n / wall * 1e3, 1),
+                                       bytes_per_frame=int(sum(len(b) for b in samples) // n),
+                                       y_psnr_db=round(10.0 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None)
+                            print(json.dumps(row), flush=True)
+                            rows.append(row)
+                            del enc, recon, samples
+                            torch.cuda.empty_cache()
+    return rows
+
+
+def main_seg(args):
+    from stable_diffusion_videos_amd import StableDiffusionWalkPipeline
+    from stable_diffusion_videos_amd.upsampling import RealESRGANModel
+    dev = torch.device("cuda", 0)
+    result = dict(tool=f"tools/h264_bench.py --gop {args.gop} --search {args.search} --subpel {args.subpel} --deblock {args.deblock} --part {args.part} "
+                       f"--qp {args.qp} --row-slices {args.row_slices}", gpu=torch.cuda.get_device_name(0), host=platform.processor() or platform.machine(),
+                  reps=args.reps, rows=[])
+    pipe = StableDiffusionWalkPipeline.from_pretrained("tiny").to(dev)
+    small = pipeline_frames(pipe, 128)
+    up = RealESRGANModel.from_pretrained("nateraw/real-esrgan")
+    up.to(dev)
+    big = torch.cat([up.upsample_u8(small[k:k + 2]) for k in range(0, 8, 2)])
+    del pipe, up
+    torch.cuda.empty_cache()
+    for name, frames in (("tiny pipeline x4 upsampler", big.contiguous()), ("tiny pipeline", small.contiguous())):
+        result["rows"] += measure_seg(name, frames, args.gops[0], args.searches, args.subpels, args.deblocks, args.parts, args.qps, args.slices, args.reps)
+        if args.out:                                                                        # (kept as it grows: a long run leaves what it measured)
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(result) + "\n")
+    line = json.dumps(result)
+    if args.out:
+        Path(args.out).write_text(line + "\n")
+    print(line)
+
+
 def main_deblock(args):
     import h264_i4_ref as I4
     import h264_me_ref as ME
@@ -509,7 +592,23 @@ def main():
     ap.add_argument("--deblock", default=None, help="D[,D...] (0, 1): one row per (qp, search, D) at one --gop N; 0 = the loop filter off")
     ap.add_argument("--qp", default=None, help="with --deblock: Q[,Q...] (0 .. 51), default 16")
     ap.add_argument("--part", default=None, help="P[,P...] (0, 1): one row per (qp, subpel, deblock, P) at one --gop N > 1 and one --search R > 0")
+    ap.add_argument("--row-slices", default=None, help="S[,S...] (1 .. 16): one row per (qp, search, subpel, deblock, part, S) at one --gop N")
     args = ap.parse_args()
+    if args.row_slices is not None:
+        args.gops = [int(v) for v in args.gop.split(",")]
+        args.search, args.subpel, args.deblock = args.search or "0", args.subpel or "0", args.deblock or "0"
+        args.part, args.qp = args.part or "0", args.qp or "16"
+        args.searches, args.subpels = [int(v) for v in args.search.split(",")], [int(v) for v in args.subpel.split(",")]
+        args.deblocks, args.parts = [int(v) for v in args.deblock.split(",")], [int(v) for v in args.part.split(",")]
+        args.qps, args.slices = [int(v) for v in args.qp.split(",")], [int(v) for v in args.row_slices.split(",")]
+        if args.intra4 is not None or len(args.gops) != 1 or not 2 <= args.gops[0] <= 256 or any(v % 2 or not 0 <= v <= 16 for v in args.searches) \
+                or any(v not in (0, 1, 2, 4) for v in args.subpels) or any(v not in (0, 1) for v in args.deblocks + args.parts) \
+                or any(not 0 <= v <= 51 for v in args.qps) or any(not 1 <= v <= 16 for v in args.slices):
+            raise SystemExit("--row-slices takes 1 .. 16, with one --gop N (2 .. 256), --search R[,R...] (even, 0 .. 16), --subpel S[,S...] (0, 1, 2, 4), "
+                             "--deblock D[,D...] (0, 1), --part P[,P...] (0, 1) and --qp Q[,Q...] (0 .. 51), without --intra4")
+        if not torch.cuda.is_available():
+            raise SystemExit("h264_bench needs the GPU (no fallback)")
+        return main_seg(args)
     if args.part is not None:
         args.gops = [int(v) for v in args.gop.split(",")]
         args.searches = [int(v) for v in (args.search or "0").split(",")]
